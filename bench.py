@@ -7,13 +7,22 @@ encoder (IR-SE50 Encoder4Editing), the StyleGAN2 synthesis and the VGG16 trunk, 
 Inputs are resident in HBM before the timed region. Rank 0 prints ONE JSON line.
 
     python bench.py [--gpus N --steps K --warmup W --batch B --dtype fp32|fp16|bf16
-                     --encoder e4e|linear --lowp fp16|bf16|none]
+                     --encoder e4e|linear --dump-outputs DIR]
+    python bench.py --full [... --lowp fp16|bf16|none --no-cpu-baseline --no-roofline]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `value` is measured at fp32, the reference's arithmetic (the reference runs its networks in
-torch's default float32 on cuda:0, code/attack/interpolation.py:1095). A reduced-precision run of
-the same workload (fp16 by default) is reported beside it as the labelled sub-record
-`low_precision` (N=1 only); it is never `value`.
+torch's default float32 on cuda:0, code/attack/interpolation.py:1095).
+
+A plain run sets up, warms up, times the K steps and prints the headline line. `--full` adds the
+rest of the record: the live HIP-event conv roofline of the timed steps, a reduced-precision run
+of the same workload (fp16 by default) as the labelled sub-record `low_precision` (N=1 only; it
+is never `value`), and the wall-clocked CPU baseline.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (the adversarial
+images; all ranks' when N>1) as DIR/adv.npy, float32; an output above DUMP_MAX_BYTES is a fixed,
+seeded sample of its elements. Inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -71,13 +80,18 @@ def parse(argv=None):
     ap.add_argument("--pgd-steps", type=int, default=20)
     ap.add_argument("--dtype", default="fp32", choices=list(DT),
                     help="compute dtype of `value` (default fp32 = the reference's precision)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the live conv roofline, "
+                         "the reduced-precision sub-record and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/adv.npy (float32)")
     ap.add_argument("--lowp", default="fp16", choices=["fp16", "bf16", "none"],
-                    help="dtype of the labelled reduced-precision sub-record (N=1 only)")
+                    help="--full: dtype of the labelled reduced-precision sub-record (N=1 only)")
     ap.add_argument("--lowp-steps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without that leg")
     ap.add_argument("--cpu-pgd-steps", type=int, default=None,
                     help="PGD iterations of the wall-clocked CPU attack (default: --pgd-steps)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--norm", default="linf", choices=["linf", "l2_cw"],
                     help="linf = PGD L∞ (the headline); l2_cw = C&W-L2 with the VGG perceptual "
                          "objective (BASELINE config #5 at --size 1024 --dtype fp16), c = 1e-4, "
@@ -327,7 +341,8 @@ def run_leg(args, dtype, steps, warmup, dev, world, rank, roofline, make_engine=
          "iters": sum(timed_cw) / len(timed_cw) if timed_cw else args.pgd_steps,
          "flops_img_step": pgd.algorithmic_flops_per_image_step(eng.G, eng.V, eng.E),
          "peak_hbm_gb": torch.cuda.max_memory_allocated(dev) / 1e9 if cuda else 0.0,
-         "output_ok": ok}
+         "output_ok": ok,
+         "output": gathered[0] if gathered else adv}  # what the last timed step returned
     if gathered:  # the all-gathered job output: n_total images, this rank's shard in place
         ga = gathered[0]
         r["gathered_ok"] = (tuple(ga.shape) == (n_total,) + tuple(adv.shape[1:])
@@ -424,6 +439,27 @@ def headline_record(args, r, world, dist_world):
     return out
 
 
+DUMP_MAX_BYTES = 48 << 20  # of float32 per dump (the headline's 128 × 3 × 256² output is 96 MiB)
+
+
+def dump_outputs(out_dir, output):
+    """Write the timed path's output as out_dir/adv.npy (float32). Above DUMP_MAX_BYTES the file
+    holds the elements at a fixed, seeded sample of flat indices (ascending), the same for every
+    run of the same shape."""
+    import numpy as np
+    flat = output.detach().reshape(-1)
+    keep = DUMP_MAX_BYTES // 4
+    if flat.numel() > keep:
+        g = torch.Generator().manual_seed(20)
+        idx = torch.randperm(flat.numel(), generator=g)[:keep].sort().values
+        flat = flat[idx.to(flat.device)]
+        log(f"--dump-outputs: seeded sample of {keep} of {output.numel()} elements")
+    else:
+        flat = flat.reshape(output.shape)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "adv.npy"), flat.float().cpu().numpy())
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -456,18 +492,24 @@ def main():
             dist.init_process_group("gloo")
         dist_world = dist.get_world_size()
     S = args.size
+    roofline = args.full and not args.no_roofline
     r = run_leg(args, args.dtype, args.steps, args.warmup, dev, world, rank,
-                not args.no_roofline, make_engine=make_engine)
+                roofline, make_engine=make_engine)
+    output = r.pop("output")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, output)
+    del output
     out = headline_record(args, r, world, dist_world)
     if "conv_busy_ms" in r:
         out["roofline"] = roofline_record(args, args.dtype, r)
-    if world == 1 and args.lowp != "none" and args.lowp != args.dtype:
+    if args.full and world == 1 and args.lowp != "none" and args.lowp != args.dtype:
         gc.collect()
         if dev.type == "cuda":
             torch.cuda.empty_cache()
         lw = max(1, min(args.warmup, 1))
         rl = run_leg(args, args.lowp, args.lowp_steps, lw, dev, world, rank,
-                     not args.no_roofline, make_engine=make_engine)
+                     roofline, make_engine=make_engine)
+        del rl["output"]
         sub = {"note": "reduced-precision run of the same workload; NOT the headline value",
                "dtype": DT_NAME[args.lowp], "value": rl["n_total"] * args.lowp_steps
                / rl["elapsed"], "unit": "attacked images/s", "steps": args.lowp_steps,
@@ -476,7 +518,7 @@ def main():
         if "conv_busy_ms" in rl:
             sub["roofline"] = roofline_record(args, args.lowp, rl)
         out["low_precision"] = sub
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(S, args.cpu_pgd_steps or args.pgd_steps, args.encoder)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -1,4 +1,5 @@
-# default bench line only
+# bench.py --full line only
 set -o pipefail
-mkdir -p gpurun_out
-timeout -k 10 400 python -u bench.py > gpurun_out/bench.log 2>&1 && echo bench-ok && tail -1 gpurun_out/bench.log | cut -c1-200
+OUT=${OUT:-run_out}
+mkdir -p "$OUT"
+timeout -k 10 400 python -u bench.py --full > "$OUT"/bench.log 2>&1 && echo bench-ok && tail -1 "$OUT"/bench.log | cut -c1-200

@@ -7,7 +7,7 @@
 set -euo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --lowp none ${EXTRA:-}"  # EXTRA="--dtype fp16"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --lowp none ${EXTRA:-}"  # EXTRA="--dtype fp16"
 T=${TAG:-}
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_trace$T \
   -o run -- python3 bench.py $ARGS > gpurun_out/prof_trace$T.log 2>&1
