@@ -136,6 +136,12 @@ SIGNATURES = {
                                c_float, c_float, c_float, P, c_int, P]),
     "mia_grad_assemble": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float,
                                   c_float, P, c_int, P]),
+    "mia_grad_assemble_norms": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int,
+                                        c_float, c_float, P, c_int, P]),
+    "mia_l2_step": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, P, P]),
+    "mia_l2_project": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, c_float, P]),
+    "mia_mi_update": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float,
+                              c_float, P, P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

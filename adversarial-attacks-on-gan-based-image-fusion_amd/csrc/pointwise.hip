@@ -919,6 +919,210 @@ __global__ void grad_assemble_kernel(const float* __restrict__ x, const float* _
   }
 }
 
+// ---- L2-ball PGD (torchattacks PGDL2) and momentum iterative FGSM (torchattacks MIFGSM) --------
+// Both need a per-image norm of the pixel gradient, so the gradient is materialised once
+// (grad_assemble_norms_kernel, with its Σ|g| and Σg²) and the updates read the norm from device
+// memory. Every kernel here runs on a (slots, N) grid, block (b, n) striding over image n alone:
+// an image's partial sums — and so its norms — depend on its own plane size only, never on the
+// other images of the call. V = 4: 16-byte accesses (plane % 4 == 0 and 16-byte aligned bases,
+// decided by the launcher); V = 1: scalar.
+template <int V>
+__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&v)[V]) {
+  if (V == 4) {
+    const f32x4 t = *(const f32x4*)p;
+#pragma unroll
+    for (int e = 0; e < V; ++e) v[e] = t[e];
+  } else {
+    v[0] = p[0];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void stv(float* __restrict__ p, const float (&v)[V]) {
+  if (V == 4) {
+    f32x4 t;
+#pragma unroll
+    for (int e = 0; e < V; ++e) t[e] = v[e];
+    *(f32x4*)p = t;
+  } else {
+    p[0] = v[0];
+  }
+}
+
+// the V per-lane accumulators of a thread, pairwise (a chain of 2 additions instead of 4)
+template <int V>
+__device__ __forceinline__ float lane_sum(const float (&a)[V]) {
+  return V == 4 ? (a[0] + a[1]) + (a[2] + a[3]) : a[0];
+}
+
+// The block's sums of s0 (quantity 0) and s1 (quantity 1, NQ = 2) into its slot blockIdx.x of
+// image blockIdx.y: wave butterflies, then the 4 wave sums in wave order (mse_sum_kernel's tree).
+// Every thread of the block must call it. part = nullptr: no quantity was asked for.
+template <int NQ>
+__device__ __forceinline__ void block_slot_store(float s0, float s1, float* __restrict__ part) {
+  __shared__ float red[2][TPB / 64];
+  s0 = wave_sum(s0);
+  if (NQ > 1) s1 = wave_sum(s1);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = s0;
+    if (NQ > 1) red[1][threadIdx.x >> 6] = s1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && part) {
+    float t0 = 0.f, t1 = 0.f;
+    for (int w = 0; w < TPB / 64; ++w) {
+      t0 += red[0][w];
+      if (NQ > 1) t1 += red[1][w];
+    }
+    red_store(part, gridDim.x, gridDim.y, 0, blockIdx.x, blockIdx.y, t0);
+    if (NQ > 1) red_store(part, gridDim.x, gridDim.y, 1, blockIdx.x, blockIdx.y, t1);
+  }
+}
+
+// g = scale·∇_x L (grad_assemble_kernel's expression: the same bits) with the per-image partial
+// sums of |g| (quantity 0) and g² (quantity 1).
+template <typename T, int V>
+__global__ __launch_bounds__(TPB) void grad_assemble_norms_kernel(
+    const float* __restrict__ x, const float* __restrict__ x0, const T* __restrict__ gv,
+    const float* __restrict__ genc, float* __restrict__ g, float* __restrict__ part, int64_t plane,
+    int S, int pf, int cpad, int enc_res, float coef_img, float scale,
+    int* __restrict__ nonfinite) {
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, nv = plane / V;
+  float a1[V], a2[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) a1[e] = a2[e] = 0.f;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < nv; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * V;
+    float xv[V], x0v[V], o[V];
+    ldv<V>(x + i0, xv);
+    ldv<V>(x0 + i0, x0v);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float v =
+          scale * assemble_grad(i0 + e, xv[e], x0v[e], gv, genc, S, pf, cpad, enc_res, coef_img);
+      if (nonfinite && !__builtin_isfinite(v)) nonfinite[n] = 1;
+      o[e] = v;
+      a1[e] += fabsf(v);
+      a2[e] += v * v;
+    }
+    stv<V>(g + i0, o);
+  }
+  block_slot_store<2>(lane_sum<V>(a1), lane_sum<V>(a2), part);
+}
+
+// torchattacks PGDL2.forward, the ascent half, on cost = −L:
+//   adv = x + a·((−g) / (‖g_n‖₂ + 1e-10)),  ‖g_n‖₂ = sqrt(gnorm2sq[n])
+// written to x un-projected, with the per-image partial sums of (adv − x0)². One fp32 rounding
+// per operation (IEEE division and square root, no contraction), as torch's fp32 CPU ops.
+template <int V>
+__global__ __launch_bounds__(TPB) void l2_step_kernel(float* __restrict__ x,
+                                                      const float* __restrict__ x0,
+                                                      const float* __restrict__ g,
+                                                      const float* __restrict__ gnorm2sq,
+                                                      float* __restrict__ part, int64_t plane,
+                                                      float a, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, nv = plane / V;
+  const float gn = sqrtf(gnorm2sq[n]) + 1e-10f;
+  if (nonfinite && threadIdx.x == 0 && !__builtin_isfinite(gn)) nonfinite[n] = 1;
+  float acc[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) acc[e] = 0.f;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < nv; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * V;
+    float xv[V], x0v[V], gg[V];
+    ldv<V>(x + i0, xv);
+    ldv<V>(x0 + i0, x0v);
+    ldv<V>(g + i0, gg);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float t = (-gg[e]) / gn;
+      if (nonfinite && !__builtin_isfinite(t)) nonfinite[n] = 1;
+      const float s = a * t;
+      const float adv = xv[e] + s;
+      const float d = adv - x0v[e];
+      const float dd = d * d;
+      acc[e] += dd;
+      xv[e] = adv;
+    }
+    stv<V>(x + i0, xv);
+  }
+  block_slot_store<1>(lane_sum<V>(acc), 0.f, part);
+}
+
+// torchattacks PGDL2.forward, the projection half: d = x − x0; f = min(e / ‖d_n‖₂, 1)
+// (e / 0 = +inf → 1); x = clamp(x0 + d·f, lo, hi), ‖d_n‖₂ = sqrt(dsq[n]).
+template <int V>
+__global__ __launch_bounds__(TPB) void l2_project_kernel(float* __restrict__ x,
+                                                         const float* __restrict__ x0,
+                                                         const float* __restrict__ dsq,
+                                                         int64_t plane, float e, float lo,
+                                                         float hi) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, nv = plane / V;
+  const float dn = sqrtf(dsq[n]);
+  const float f = fminf(e / dn, 1.f);
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < nv; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * V;
+    float xv[V], x0v[V];
+    ldv<V>(x + i0, xv);
+    ldv<V>(x0 + i0, x0v);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float d = xv[k] - x0v[k];
+      const float df = d * f;
+      const float r = x0v[k] + df;
+      xv[k] = fminf(fmaxf(r, lo), hi);
+    }
+    stv<V>(x + i0, xv);
+  }
+}
+
+// torchattacks MIFGSM.forward on cost = −L, one pass:
+//   ĝ = (−g) / (l1[n] / plane);  m = ĝ + μ·m;
+//   x = clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), lo, hi)
+// One fp32 rounding per operation. A non-finite ĝ (zero or non-finite mean, 0/0) marks the image.
+template <int V>
+__global__ __launch_bounds__(TPB) void mi_update_kernel(float* __restrict__ x,
+                                                        const float* __restrict__ x0,
+                                                        const float* __restrict__ g,
+                                                        const float* __restrict__ l1,
+                                                        float* __restrict__ m, int64_t plane,
+                                                        float mu, float a, float e, float lo,
+                                                        float hi, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, nv = plane / V;
+  const float mean = l1[n] / (float)plane;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < nv; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * V;
+    float xv[V], x0v[V], gg[V], mv[V];
+    ldv<V>(x + i0, xv);
+    ldv<V>(x0 + i0, x0v);
+    ldv<V>(g + i0, gg);
+    ldv<V>(m + i0, mv);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float gh = (-gg[k]) / mean;
+      if (nonfinite && !__builtin_isfinite(gh)) nonfinite[n] = 1;
+      const float dec = mu * mv[k];
+      const float mm = gh + dec;
+      mv[k] = mm;
+      const float sg = mm > 0.f ? 1.f : (mm < 0.f ? -1.f : 0.f);
+      const float adv = xv[k] + a * sg;
+      float d = adv - x0v[k];
+      d = fminf(fmaxf(d, -e), e);
+      const float r = x0v[k] + d;
+      xv[k] = fminf(fmaxf(r, lo), hi);
+    }
+    stv<V>(m + i0, mv);
+    stv<V>(x + i0, xv);
+  }
+}
+
 // ---- C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1, 1]:
 // adv = tanh(w) (= 2·½(tanh w + 1) − 1), w0 = atanh(x) with x clamped to ±(1 − 2⁻²⁰) so that
 // saturated pixels stay finite.
@@ -1388,6 +1592,102 @@ extern "C" int mia_grad_assemble(const float* x, const float* x0, const void* g_
                  x0, (const T*)g_vgg, g_enc, g, N, S, pf, cpad, enc_res, coef_img, scale,
                  nonfinite));
   return MIA_OK;
+}
+
+// (slots, N) grid of the per-image passes: ≤ 1024 slots of TPB threads, each moving V floats
+static inline dim3 image_grid(int64_t plane, int V, int N) {
+  return dim3(blocks_for(plane / V, TPB, 1024), N);
+}
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+#define MIA_CHECK_IMAGES(N, plane)                                                      \
+  MIA_CHECK_ARG((N) > 0 && (N) <= 65535, "N must be in 1 … 65535");                     \
+  MIA_CHECK_ARG((plane) > 0 && (plane) < (1LL << 31), "plane must be in 1 … 2^31 − 1")
+
+extern "C" int mia_grad_assemble_norms(const float* x, const float* x0, const void* g_vgg,
+                                       const float* g_enc, float* g, float* l1, float* l2sq,
+                                       int N, int S, int pf, int cpad, int enc_res,
+                                       float coef_img, float scale, int* nonfinite, int dtype,
+                                       void* stream) {
+  MIA_CHECK_ARG(x && x0 && g, "null x / x0 / g");
+  MIA_CHECK_ARG(S > 0 && S <= 16384, "S must be in 1 … 16384");
+  const int64_t plane = (int64_t)3 * S * S;
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(pf >= 1 && S % pf == 0, "pf must divide S");
+  MIA_CHECK_ARG(!g_vgg || cpad >= 3, "cpad must be >= 3");
+  MIA_CHECK_ARG(!g_enc || (enc_res >= 1 && S % enc_res == 0), "enc_res must divide S");
+  MIA_CHECK_ARG(dtype == MIA_F32 || dtype == MIA_F16 || dtype == MIA_BF16, "unsupported dtype");
+  if (!g_enc) enc_res = S;  // unused, but the kernel divides by S / enc_res
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(x0) && aligned16(g);
+  const dim3 grid = image_grid(plane, vec ? 4 : 1, N);
+  RedQ r;
+  int rc = red_begin(r, l1, l2sq, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  MIA_DISPATCH_DTYPE(dtype, T,
+      if (vec) {
+        hipLaunchKernelGGL((grad_assemble_norms_kernel<T, 4>), grid, dim3(TPB), 0, st, x, x0,
+                           (const T*)g_vgg, g_enc, g, r.part, plane, S, pf, cpad, enc_res,
+                           coef_img, scale, nonfinite);
+      } else {
+        hipLaunchKernelGGL((grad_assemble_norms_kernel<T, 1>), grid, dim3(TPB), 0, st, x, x0,
+                           (const T*)g_vgg, g_enc, g, r.part, plane, S, pf, cpad, enc_res,
+                           coef_img, scale, nonfinite);
+      });
+  rc = check_launch("grad_assemble_norms_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+extern "C" int mia_l2_step(float* x, const float* x0, const float* g, const float* gnorm2sq,
+                           float* dsq_out, int N, int64_t plane, float a, int* nonfinite,
+                           void* stream) {
+  MIA_CHECK_ARG(x && x0 && g && gnorm2sq && dsq_out, "null argument");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(a > 0.f, "the step a must be > 0");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(x0) && aligned16(g);
+  const dim3 grid = image_grid(plane, vec ? 4 : 1, N);
+  RedQ r;
+  int rc = red_begin(r, dsq_out, nullptr, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  if (vec)
+    hipLaunchKernelGGL(l2_step_kernel<4>, grid, dim3(TPB), 0, st, x, x0, g, gnorm2sq, r.part,
+                       plane, a, nonfinite);
+  else
+    hipLaunchKernelGGL(l2_step_kernel<1>, grid, dim3(TPB), 0, st, x, x0, g, gnorm2sq, r.part,
+                       plane, a, nonfinite);
+  rc = check_launch("l2_step_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+extern "C" int mia_l2_project(float* x, const float* x0, const float* dsq, int N, int64_t plane,
+                              float e, float lo, float hi, void* stream) {
+  MIA_CHECK_ARG(x && x0 && dsq, "null argument");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(e > 0.f && lo <= hi, "need e > 0 and lo <= hi");
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(x0);
+  const dim3 grid = image_grid(plane, vec ? 4 : 1, N);
+  if (vec)
+    MIA_LAUNCH(l2_project_kernel<4>, grid, dim3(TPB), 0, x, x0, dsq, plane, e, lo, hi);
+  MIA_LAUNCH(l2_project_kernel<1>, grid, dim3(TPB), 0, x, x0, dsq, plane, e, lo, hi);
+}
+
+extern "C" int mia_mi_update(float* x, const float* x0, const float* g, const float* l1, float* m,
+                             int N, int64_t plane, float mu, float a, float e, float lo, float hi,
+                             int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(x && x0 && g && l1 && m, "null argument");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(mu >= 0.f && a > 0.f && e > 0.f && lo <= hi,
+                "need mu >= 0, a > 0, e > 0 and lo <= hi");
+  const bool vec =
+      plane % 4 == 0 && aligned16(x) && aligned16(x0) && aligned16(g) && aligned16(m);
+  const dim3 grid = image_grid(plane, vec ? 4 : 1, N);
+  if (vec)
+    MIA_LAUNCH(mi_update_kernel<4>, grid, dim3(TPB), 0, x, x0, g, l1, m, plane, mu, a, e, lo, hi,
+               nonfinite);
+  MIA_LAUNCH(mi_update_kernel<1>, grid, dim3(TPB), 0, x, x0, g, l1, m, plane, mu, a, e, lo, hi,
+             nonfinite);
 }
 
 extern "C" int mia_cw_init(const float* x, float* w, int64_t len, void* stream) {

@@ -47,8 +47,8 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     * A rank whose shard is empty (world > n) runs no attack and contributes only the zero padding
       of the all-gather (every rank must still enter the collective).
     * The random-start noise is drawn ONCE for the full batch from ``seed`` (the same host draw as
-      a single-GPU ``attack(..., random_start=True, seed=seed)``) and sliced per shard, so the
-      output does not depend on the world size.
+      a single-GPU ``attack(..., random_start=True, seed=seed)``, the unit-L2-ball draw for
+      ``norm="l2"``) and sliced per shard, so the output does not depend on the world size.
     * fp16 loss-scale overflows are decided job-wide (``pgd.rescale_consensus``, one int32 MAX
       all-reduce per attack run): every shard re-runs at the same λ, and a fatal overflow raises
       FloatingPointError on EVERY rank (an empty-shard rank included) before the all-gather, so
@@ -67,7 +67,8 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     tgt = target if target.shape[0] == 1 else target[lo:hi]
     noise = None
     if random_start:
-        noise = pgd.make_start_noise(tuple(imgs.shape), seed)[lo:hi]
+        noise_norm = "l2" if kw.get("norm", "linf") == "l2" else "linf"
+        noise = pgd.make_start_noise(tuple(imgs.shape), seed, noise_norm)[lo:hi]
     local = pgd.attack(net, imgs[lo:hi], eps, steps, target=tgt, random_start=random_start,
                        seed=seed, start_noise=noise, group=group, **kw)
     return gather_shards(local.to(gather_dev, torch.float32), n, group).to(imgs.device)

@@ -532,6 +532,79 @@ def grad_assemble(x, x0, g_vgg, g_enc, g, pf, enc_res, coef_img, scale=1.0, nonf
     return g
 
 
+def grad_assemble_norms(x, x0, g_vgg, g_enc, g, l1, l2sq, pf, enc_res, coef_img, scale=1.0,
+                        nonfinite=None):
+    """grad_assemble plus l1[n] += Σ|g_n| and l2sq[n] += Σ g_n² (either may be None), in one pass
+    (mia_grad_assemble_norms)."""
+    N, C, S, S2 = x.shape
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    if C != 3 or S != S2:
+        raise ValueError("x must be (N,3,S,S)")
+    _need(x, x.shape, torch.float32, "x")
+    _need(x0, x.shape, torch.float32, "x0")
+    _need(g, x.shape, torch.float32, "g")
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    if pf < 1 or S % pf:
+        raise ValueError("pf must divide S")
+    R = S // pf
+    cpad = g_vgg.shape[-1] if g_vgg is not None else 8
+    if g_vgg is not None:
+        _need(g_vgg, (N, R, R, cpad), None, "g_vgg")
+    if g_enc is not None:
+        _need(g_enc, (N, 3, enc_res, enc_res), torch.float32, "g_enc")
+    T = g_vgg.dtype if g_vgg is not None else torch.float32
+    call("mia_grad_assemble_norms", ptr(x), ptr(x0), ptr(g_vgg), ptr(g_enc), ptr(g), ptr(l1),
+         ptr(l2sq), N, S, pf, cpad, enc_res, float(coef_img), float(scale), ptr(nonfinite), dt(T),
+         stream())
+    return g
+
+
+def _image_rows(x, name="x"):
+    """(N, elements per image) of a batch of fp32 images."""
+    if x.dim() < 2 or x.dtype != torch.float32 or x.shape[0] < 1:
+        raise ValueError(f"{name} must be a non-empty fp32 batch of images")
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+def l2_step(x, x0, g, gnorm2sq, dsq, a, nonfinite=None):
+    """x ← x + a·((−g)/(√gnorm2sq[n] + 1e-10)) (un-projected); dsq[n] += Σ(x − x0)²
+    (mia_l2_step)."""
+    N, plane = _image_rows(x)
+    _need(x0, x.shape, torch.float32, "x0")
+    _need(g, x.shape, torch.float32, "g")
+    _need(gnorm2sq, (N,), torch.float32, "gnorm2sq")
+    _need(dsq, (N,), torch.float32, "dsq")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    call("mia_l2_step", ptr(x), ptr(x0), ptr(g), ptr(gnorm2sq), ptr(dsq), N, plane, float(a),
+         ptr(nonfinite), stream())
+    return x
+
+
+def l2_project(x, x0, dsq, e, lo=-1.0, hi=1.0):
+    """x ← clamp(x0 + (x − x0)·min(e/√dsq[n], 1), lo, hi) (mia_l2_project)."""
+    N, plane = _image_rows(x)
+    _need(x0, x.shape, torch.float32, "x0")
+    _need(dsq, (N,), torch.float32, "dsq")
+    call("mia_l2_project", ptr(x), ptr(x0), ptr(dsq), N, plane, float(e), float(lo), float(hi),
+         stream())
+    return x
+
+
+def mi_update(x, x0, g, l1, m, mu, a, e, lo=-1.0, hi=1.0, nonfinite=None):
+    """m ← (−g)/(l1[n]/plane) + mu·m; x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), lo, hi)
+    (mia_mi_update)."""
+    N, plane = _image_rows(x)
+    _need(x0, x.shape, torch.float32, "x0")
+    _need(g, x.shape, torch.float32, "g")
+    _need(m, x.shape, torch.float32, "m")
+    _need(l1, (N,), torch.float32, "l1")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    call("mia_mi_update", ptr(x), ptr(x0), ptr(g), ptr(l1), ptr(m), N, plane, float(mu), float(a),
+         float(e), float(lo), float(hi), ptr(nonfinite), stream())
+    return x
+
+
 def cw_init(x, w):
     _need(w, x.shape, torch.float32, "w")
     call("mia_cw_init", ptr(x), ptr(w), x.numel(), stream())

@@ -405,6 +405,76 @@ class AttackEngine:
             self.step(x, a, e)
         return x.clone()
 
+    def _start(self, x0, t, e, random_start, start_noise):
+        """prepare() and the iterate buffer at x0 (or clamp(x0 + e·noise) for a random start)."""
+        self.prepare(x0, t)
+        x = self.ws.get("adv", x0.shape, torch.float32)
+        x.copy_(x0)
+        if random_start:
+            if start_noise is None:
+                raise ValueError("random_start needs start_noise (make_start_noise)")
+            ops.random_start(x, x0, start_noise, e)
+        return x
+
+    def _grad_norms(self, x, g, l1, l2sq):
+        """g ← ∇_x L at x, UNSCALED (scale 1/λ: the normalised steps divide by the gradient's own
+        norm, which must not overflow with λ), with its per-image Σ|g| / Σg² (device-resident)."""
+        g_xv, g_enc = self.gradient(x)
+        ops.grad_assemble_norms(x, self.x0, g_xv, g_enc, g, l1, l2sq, self.pf, ENC_POOL_RES,
+                                self.c_img_o, 1.0 / self.loss_scale, nonfinite=self.nonfinite)
+
+    def step_l2(self, x, a, e):
+        """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units."""
+        g = self.ws.get("g.full", x.shape, torch.float32)
+        sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
+        self._grad_norms(x, g, None, sums[0])  # sums: Σg², Σ(adv − x0)² per image
+        ops.l2_step(x, self.x0, g, sums[0], sums[1], _f32(a), nonfinite=self.nonfinite)
+        ops.l2_project(x, self.x0, sums[1], _f32(e))
+        return x
+
+    def step_mi(self, x, m, momentum, a, e):
+        """One momentum iterative FGSM step on x and the momentum buffer m, both in place."""
+        g = self.ws.get("g.full", x.shape, torch.float32)
+        l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
+        self._grad_norms(x, g, l1, None)
+        ops.mi_update(x, self.x0, g, l1, m, _f32(momentum), _f32(a), _f32(e),
+                      nonfinite=self.nonfinite)
+        return x
+
+    def run_l2(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None):
+        """L2-ball PGD (torchattacks PGDL2.forward) descending L: per image
+        x ← x + a·(−g)/(‖g‖₂ + 1e-10); d = x − x0; x ← clamp(x0 + d·min(e/‖d‖₂, 1), −1, 1), with
+        e = 2·eps, a = 2·alpha. ``start_noise``: make_start_noise(shape, seed, "l2"). The norms
+        stay on the device (ordered reductions): no per-step host synchronisation."""
+        return self._with_rescale(
+            lambda: self._run_l2(x0, t, steps, eps, alpha, random_start, start_noise), group)
+
+    def _run_l2(self, x0, t, steps, eps, alpha, random_start, start_noise):
+        e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
+        x = self._start(x0, t, e, random_start, start_noise)
+        for _ in range(steps):
+            self.step_l2(x, a, e)
+        return x.clone()
+
+    def run_mi(self, x0, t, steps, eps, alpha, momentum=1.0, random_start=False, start_noise=None,
+               group=None):
+        """Momentum iterative FGSM (torchattacks MIFGSM.forward) descending L: per image
+        ĝ = (−g)/mean|g|; m ← ĝ + μ·m (m = 0 at the start);
+        x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1), with e = 2·eps, a = 2·alpha.
+        An image whose gradient is all zero (0/0) is reported like an overflow, never left frozen
+        silently."""
+        return self._with_rescale(
+            lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise),
+            group)
+
+    def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise):
+        e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
+        x = self._start(x0, t, e, random_start, start_noise)
+        m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
+        for _ in range(steps):
+            self.step_mi(x, m, momentum, a, e)
+        return x.clone()
+
 
 def _check_images(imgs, size, name):
     if not torch.is_tensor(imgs) or imgs.dim() != 4 or imgs.shape[1] != 3:
@@ -415,43 +485,74 @@ def _check_images(imgs, size, name):
         raise ValueError(f"{name} must be floating point")
 
 
-NORMS = ("linf", "adam", "l2_cw")
+NORMS = ("linf", "l2", "adam", "l2_cw")
 
 
-def make_start_noise(shape, seed):
-    """The random-start draw: host-seeded U(-1,1) of the FULL batch shape (scaled by e in the
-    kernel); ``attack_distributed`` slices it per shard so every world size sees the same noise."""
+def make_start_noise(shape, seed, norm="linf"):
+    """The random-start draw of the FULL batch shape (scaled by e in the kernel, x = clamp(x0 +
+    e·u)); ``attack_distributed`` slices it per shard so every world size sees the same noise.
+
+    'linf': host-seeded U(-1,1) per element. 'l2': per image a point of the unit L2 ball by
+    torchattacks PGDL2's construction — a Gaussian direction, normalised (‖·‖₂ + 1e-10), times
+    r ~ U(0,1). This matches torchattacks in distribution, not in rounding order (there e
+    multiplies r before the direction; here the kernel multiplies the finished sample)."""
     g = torch.Generator().manual_seed(int(seed))
-    return torch.rand(shape, generator=g) * 2 - 1
+    if norm == "linf":
+        return torch.rand(shape, generator=g) * 2 - 1
+    if norm != "l2":
+        raise ValueError("start noise exists for norm 'linf' and 'l2'")
+    shape = tuple(shape)
+    d = torch.randn(shape, generator=g)
+    r = torch.rand((shape[0],), generator=g)
+    nrm = d.reshape(shape[0], -1).norm(p=2, dim=1) + 1e-10
+    return d * (r / nrm).reshape((-1,) + (1,) * (len(shape) - 1))
 
 
 def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_start=False,
-           seed=0, start_noise=None, norm="linf", loss="gan_vgg", loss_scale=None, lr=0.01,
-           cw_c=1e-4, return_info=False, group=None):
+           seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
+           lr=0.01, cw_c=1e-4, return_info=False, group=None):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
             (built by ``gfa_amd.networks.build_net``); may also carry ``net.vgg``.
     imgs    (N,3,S,S) float tensor in [-1,1] (reference normalisation, transforms_config.py:29-31),
             on CPU or GPU; not modified.
-    eps     L∞ radius in [0,1] pixel units (8/255 in the reference's PGD call, interpolation.py:1343).
+    eps     radius in [0,1] pixel units: L∞ for norm='linf' (8/255 in the reference's PGD call,
+            interpolation.py:1343), per-image L2 for norm='l2'.
     steps   iterations (PGD: 1 with alpha=eps and random_start=False is FGSM).
     alpha   PGD step in [0,1] pixel units; default 0.01 = the reference's PGD call
-            (interpolation.py:1343; torchattacks' own default is 2/255).
-    start_noise  optional host U(-1,1) tensor of imgs' shape for random_start (default: drawn
-            from ``seed`` by ``make_start_noise(imgs.shape, seed)``).
+            (interpolation.py:1343; torchattacks' own default is 2/255). That default is sized
+            for L∞: for norm='l2' the step is an L2 length, pass alpha ≈ eps/5 (torchattacks
+            PGDL2's own ratio, eps = 1.0 with alpha = 0.2).
+    start_noise  optional host tensor of imgs' shape for random_start (default: drawn from
+            ``seed`` by ``make_start_noise(imgs.shape, seed, norm)``: U(-1,1) per element for
+            'linf', a point of the unit L2 ball per image for 'l2').
     target  white-box target image(s) (N or 1, 3, S, S) — the ``img_target`` of optimize_vgg.
     norm    'linf'  — torchattacks PGD rule (interpolation.py:62-96) on the objective;
+            'l2'    — torchattacks PGDL2 rule, per image in [-1,1] space (e = 2·eps, a = 2·alpha):
+                      x ← x + a·(−∇L)/(‖∇L‖₂ + 1e-10); d = x − x0;
+                      x ← clamp(x0 + d·min(e/‖d‖₂, 1), −1, 1)   (AttackEngine.run_l2);
             'adam'  — optimize_vgg literal (interpolation.py:743-843): Adam(lr) on the pixels,
                       no ε-ball (eps is ignored and may be None);
             'l2_cw' — torchattacks C&W L2 (interpolation.py:98-193) with f = the objective,
                       c = cw_c, Adam(lr) in tanh space (eps ignored; see AttackEngine.run_cw).
+    momentum  None (default): the plain rule of ``norm``. μ ≥ 0, with norm='linf' only: the
+            torchattacks MIFGSM rule, per image with a momentum buffer m (0 at the start):
+                      ĝ = (−∇L)/mean|∇L|; m ← ĝ + μ·m;
+                      x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1)
+            (AttackEngine.run_mi; torchattacks' default decay is 1.0). An image whose gradient
+            is entirely zero raises FloatingPointError instead of staying frozen.
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
     Returns the adversarial images on the input's device (fp32), and a dict if return_info.
     """
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}")
+    if momentum is not None:
+        if norm != "linf":
+            raise ValueError("momentum (MI-FGSM) is implemented for norm='linf' only")
+        if not float(momentum) >= 0:
+            raise ValueError("momentum must be >= 0")
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
@@ -467,15 +568,20 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         raise ValueError("target batch must be 1 or match imgs")
     if steps < 0 or int(steps) != steps:
         raise ValueError("need integer steps >= 0")
-    if norm == "linf" and not (eps is not None and eps > 0 and alpha > 0):
+    if norm in ("linf", "l2") and not (eps is not None and eps > 0 and alpha > 0):
         raise ValueError("PGD needs eps > 0 and alpha > 0")
-    if norm != "linf" and not lr > 0:
+    if norm in ("adam", "l2_cw") and not lr > 0:
         raise ValueError("lr must be > 0")
     if float(imgs.min()) < -1.0 or float(imgs.max()) > 1.0:
         raise ValueError("imgs must lie in [-1, 1]")
     vgg = vgg if vgg is not None else getattr(net, "vgg", None)
     if vgg is None:
         raise ValueError("a VGG feature network is required (optimize_vgg's vgg)")
+    for name, part in (("net.encoder", getattr(net, "encoder", None)),
+                       ("net.decoder", net.decoder), ("vgg", vgg)):
+        if not hasattr(part, "impl"):
+            raise ValueError(f"{name} must be a device network of this package "
+                             "(networks.build_net / build_net_from_checkpoint, vgg16)")
     dev = net.decoder.device
     x0 = imgs.detach().to(dev, torch.float32).contiguous()
     t = target.detach().to(dev, torch.float32).contiguous()
@@ -483,13 +589,20 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     noise = None
     if random_start:
         if start_noise is None:
-            start_noise = make_start_noise(tuple(x0.shape), seed)
+            start_noise = make_start_noise(tuple(x0.shape), seed,
+                                           "l2" if norm == "l2" else "linf")
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf":
+    if norm == "linf" and momentum is not None:
+        adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha), float(momentum),
+                         random_start, noise, group=group)
+    elif norm == "linf":
         adv = eng.run(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
                       group=group)
+    elif norm == "l2":
+        adv = eng.run_l2(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
+                         group=group)
     elif norm == "adam":
         adv = eng.run_adam(x0, t, int(steps), lr=float(lr), group=group)
     else:
@@ -497,7 +610,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     adv = adv.to(imgs.device)
     if return_info:
         info = dict(loss=eng.loss(adv.to(dev)), steps=int(steps), eps=eps, alpha=alpha, norm=norm,
-                    dtype=str(eng.dtype), loss_scale=eng.loss_scale, rescales=eng.rescales)
+                    momentum=momentum, dtype=str(eng.dtype), loss_scale=eng.loss_scale,
+                    rescales=eng.rescales)
         return adv, info
     return adv
 

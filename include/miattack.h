@@ -386,6 +386,42 @@ int mia_pgd_update(float* x, const float* x0, const void* g_vgg, const float* g_
 int mia_grad_assemble(const float* x, const float* x0, const void* g_vgg, const float* g_enc,
                       float* g, int N, int S, int pf, int cpad, int enc_res, float coef_img,
                       float scale, int* nonfinite, int dtype, void* stream);
+/* mia_grad_assemble with the per-image norms of the gradient it writes, in one pass:
+ *   g = scale·∇_x L (the same bits as mia_grad_assemble),  l1[n] += Σ|g_n|,  l2sq[n] += Σ g_n²
+ * over the 3·S² elements of image n (l1 / l2sq: fp32 [N], either may be NULL). The sums are
+ * ordered reductions (see "Deterministic reductions" above): at most 1024 per-block partials
+ * per image, added in a fixed order that depends on S only — bit-identical run to run, and an
+ * image's sums do not depend on the other images of the call. (3·S² % 4 == 0 with 16-byte
+ * aligned x / x0 / g moves 16-byte vectors, anything else scalars; the two forms add in
+ * different orders, so keep a tensor's alignment fixed where bits are compared.) They feed mia_l2_step (torchattacks
+ * PGDL2: grad / (‖grad‖₂ + 1e-10)) and mia_mi_update (torchattacks MIFGSM: grad / mean|grad|)
+ * from device memory, with no host round trip. */
+int mia_grad_assemble_norms(const float* x, const float* x0, const void* g_vgg,
+                            const float* g_enc, float* g, float* l1, float* l2sq, int N, int S,
+                            int pf, int cpad, int enc_res, float coef_img, float scale,
+                            int* nonfinite, int dtype, void* stream);
+/* L2-ball PGD, the ascent half (torchattacks PGDL2.forward on cost = −L), per image n of `plane`
+ * fp32 elements:
+ *   adv = x + a·((−g) / (sqrt(gnorm2sq[n]) + 1e-10))        (x in place, NOT yet projected)
+ *   dsq_out[n] += Σ (adv − x0)²                             (ordered reduction, as above)
+ * One fp32 rounding per operation (IEEE division / square root, no contraction): for the same g
+ * and gnorm2sq the result equals torch's fp32 CPU ops bit for bit. nonfinite (NULL or int[N]) is
+ * set for an image with a non-finite norm or normalised gradient element. */
+int mia_l2_step(float* x, const float* x0, const float* g, const float* gnorm2sq, float* dsq_out,
+                int N, int64_t plane, float a, int* nonfinite, void* stream);
+/* L2-ball PGD, the projection half (torchattacks PGDL2.forward): d = x − x0;
+ *   f = min(e / sqrt(dsq[n]), 1)   (e / 0 = +inf → 1; one IEEE division);
+ *   x = clamp(x0 + d·f, lo, hi)    (in place). Bit-exact vs torch fp32 ops as above. */
+int mia_l2_project(float* x, const float* x0, const float* dsq, int N, int64_t plane, float e,
+                   float lo, float hi, void* stream);
+/* Momentum iterative FGSM step (torchattacks MIFGSM.forward on cost = −L), one pass per image n:
+ *   ĝ = (−g) / (l1[n] / plane);   m = ĝ + mu·m   (m: fp32, x's shape, zero before the first step)
+ *   x = clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), lo, hi)   (in place)
+ * Bit-exact vs torch fp32 ops as above. nonfinite is set for an image with a non-finite ĝ element
+ * (a zero or non-finite mean, 0/0): its pixels would otherwise freeze silently. */
+int mia_mi_update(float* x, const float* x0, const float* g, const float* l1, float* m, int N,
+                  int64_t plane, float mu, float a, float e, float lo, float hi, int* nonfinite,
+                  void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);

@@ -103,6 +103,38 @@ int main() {
                                nullptr), "mse_fwd_bwd no output");
   expect_error(mia_mse_fwd_bwd(dummy, dummy, dummy, dummy, 1, 64, 1.f, 1.f, 1, MIA_F16, nullptr),
                "mse_fwd_bwd fp16 accumulate");
+  // the L2-ball PGD / momentum updates: null pointers, empty batches, shapes that do not fit
+  expect_error(mia_grad_assemble_norms(nullptr, dummy, nullptr, nullptr, dummy, dummy, dummy, 2,
+                                       32, 1, 8, 16, 1.f, 1.f, nullptr, MIA_F32, nullptr),
+               "grad_assemble_norms null x");
+  expect_error(mia_grad_assemble_norms(dummy, dummy, nullptr, nullptr, dummy, dummy, dummy, 0, 32,
+                                       1, 8, 16, 1.f, 1.f, nullptr, MIA_F32, nullptr),
+               "grad_assemble_norms N");
+  expect_error(mia_grad_assemble_norms(dummy, dummy, dummy, nullptr, dummy, dummy, dummy, 2, 32, 3,
+                                       8, 16, 1.f, 1.f, nullptr, MIA_F32, nullptr),
+               "grad_assemble_norms pf");
+  expect_error(mia_grad_assemble_norms(dummy, dummy, nullptr, dummy, dummy, dummy, dummy, 2, 32, 1,
+                                       8, 5, 1.f, 1.f, nullptr, MIA_F32, nullptr),
+               "grad_assemble_norms enc_res");
+  expect_error(mia_grad_assemble_norms(dummy, dummy, nullptr, nullptr, dummy, dummy, dummy, 2, 32,
+                                       1, 8, 16, 1.f, 1.f, nullptr, 99, nullptr),
+               "grad_assemble_norms dtype");
+  expect_error(mia_l2_step(dummy, dummy, dummy, nullptr, dummy, 2, 3072, 0.1f, nullptr, nullptr),
+               "l2_step null norm");
+  expect_error(mia_l2_step(dummy, dummy, dummy, dummy, dummy, -1, 3072, 0.1f, nullptr, nullptr),
+               "l2_step N");
+  expect_error(mia_l2_step(dummy, dummy, dummy, dummy, dummy, 2, 0, 0.1f, nullptr, nullptr),
+               "l2_step plane");
+  expect_error(mia_l2_project(dummy, nullptr, dummy, 2, 3072, 0.1f, -1.f, 1.f, nullptr),
+               "l2_project null x0");
+  expect_error(mia_l2_project(dummy, dummy, dummy, 2, 3072, 0.f, -1.f, 1.f, nullptr),
+               "l2_project e");
+  expect_error(mia_mi_update(dummy, dummy, dummy, dummy, nullptr, 2, 3072, 1.f, 0.1f, 0.1f, -1.f,
+                             1.f, nullptr, nullptr), "mi_update null m");
+  expect_error(mia_mi_update(dummy, dummy, dummy, dummy, dummy, 2, 3072, -1.f, 0.1f, 0.1f, -1.f,
+                             1.f, nullptr, nullptr), "mi_update mu");
+  expect_error(mia_mi_update(dummy, dummy, dummy, dummy, dummy, 1 << 20, 3072, 1.f, 0.1f, 0.1f,
+                             -1.f, 1.f, nullptr, nullptr), "mi_update N");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
