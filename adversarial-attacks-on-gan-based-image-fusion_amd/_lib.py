@@ -142,6 +142,7 @@ SIGNATURES = {
     "mia_l2_project": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, c_float, P]),
     "mia_mi_update": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float,
                               c_float, P, P]),
+    "mia_ti_smooth_norms": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

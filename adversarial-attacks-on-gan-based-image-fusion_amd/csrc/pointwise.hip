@@ -1123,6 +1123,188 @@ __global__ __launch_bounds__(TPB) void mi_update_kernel(float* __restrict__ x,
   }
 }
 
+// ---- translation-invariant smoothing (torchattacks TIFGSM): gs = (taps ⊗ taps) ⋆ g per plane,
+// zero padded, with the per-image partial sums of |gs| (quantity 0) and gs² (quantity 1).
+// One block = one TI_T × TI_T output tile of one plane, on a (C·tiles, N) grid: the geometry
+// depends on (C, H, W) only. Three phases over LDS:
+//   A  the tile with its halo (zero outside the plane), r = K/2 rows above / below and
+//      rl = r rounded up to 4 columns left / right, so that a 16-byte global vector is whole;
+//   B  the horizontal pass over every row of A;
+//   the vertical pass over B, into registers, stored with the sums.
+// Every output is t[0]·v[0] followed by fma(t[k], v[k], ·) for k = 1 … K−1 in both passes: its
+// value depends on its plane and position only, never on the tile layout or the batch. The taps
+// are staged in LDS and read as uniform 16-byte vectors, 8 taps per loop trip.
+// LDS banking: A's row stride is odd, so the 4 rows × 8 column groups that a 32-lane half reads
+// in the horizontal pass (ds_read_b32, bank = dword mod 32) fall on 32 distinct banks, and so do
+// the vector path's stores; B's rows are 64 dwords, written and read as whole 16-byte slots.
+constexpr int TI_T = 64;     // tile edge
+constexpr int TI_MAXK = 63;  // largest kernel
+constexpr int TI_OFFA = 68;  // LDS floats [0, 68): 3 unused, the taps, zeros up to a whole vector
+
+struct TiGeom {
+  int r, rl, HA, WA, SA, offB, floats;
+  __host__ __device__ explicit TiGeom(int K) {
+    r = K >> 1;
+    rl = (r + 3) & ~3;
+    HA = TI_T + K - 1;
+    WA = TI_T + 2 * rl;
+    SA = WA + 3;  // odd; the passes prefetch up to 2 elements / rows past their last operand
+    offB = (TI_OFFA + HA * SA + 3) & ~3;
+    floats = offB + (HA + 2) * TI_T;
+  }
+};
+
+__device__ __forceinline__ float ti_fma(float t, float v, float acc) { return fmaf(t, v, acc); }
+__device__ __forceinline__ f32x4 ti_fma(float t, f32x4 v, f32x4 acc) {
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = fmaf(t, v[e], acc[e]);
+  return o;
+}
+
+// Taps k … k + 2·NP − 1 (k ≡ 1 mod 8, tk = &taps[k], 16-byte aligned) added to the 4 outputs
+// acc[o] = Σ t[j]·in[o + j]; in[j] = *(T*)(src + j·stride) lives in w[j & 7]. On entry w holds
+// in[k … k + 4]; every pair of taps first fetches the two inputs that the NEXT pair adds.
+template <typename T, int NP>
+__device__ __forceinline__ void ti_pairs(const float* __restrict__ src, int stride, int k,
+                                         const float* __restrict__ tk, T (&w)[8], T (&acc)[4]) {
+  float tv[8];
+#pragma unroll
+  for (int j = 0; j < (2 * NP + 3) / 4; ++j) {
+    const f32x4 v = *(const f32x4*)(tk + 4 * j);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tv[4 * j + e] = v[e];
+  }
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    constexpr int ph = 1;  // k & 7
+    const int kk = ph + 2 * p;
+    w[(kk + 5) & 7] = *(const T*)(src + (k + 2 * p + 5) * stride);
+    w[(kk + 6) & 7] = *(const T*)(src + (k + 2 * p + 6) * stride);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc[o] = ti_fma(tv[2 * p], w[(kk + o) & 7], acc[o]);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc[o] = ti_fma(tv[2 * p + 1], w[(kk + 1 + o) & 7], acc[o]);
+  }
+}
+
+// acc[o] = Σ_{j<K} t[j]·in[o + j] for o = 0 … 3 in tap order (K odd: tap 0, then pairs); reads up
+// to in[K + 4], two past the last operand. tapS[3 + j] = t[j].
+template <typename T>
+__device__ __forceinline__ void ti_filter(const float* __restrict__ src, int stride,
+                                          const float* __restrict__ tapS, int K, T (&acc)[4]) {
+  T w[8];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) w[j] = *(const T*)(src + j * stride);
+  const float t0 = tapS[3];
+#pragma unroll
+  for (int o = 0; o < 4; ++o) acc[o] = t0 * w[o];
+  int k = 1;
+  for (; k + 8 <= K; k += 8) ti_pairs<T, 4>(src, stride, k, tapS + 3 + k, w, acc);
+  switch ((K - k) >> 1) {
+    case 1: ti_pairs<T, 1>(src, stride, k, tapS + 3 + k, w, acc); break;
+    case 2: ti_pairs<T, 2>(src, stride, k, tapS + 3 + k, w, acc); break;
+    case 3: ti_pairs<T, 3>(src, stride, k, tapS + 3 + k, w, acc); break;
+    default: break;
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(TPB) void ti_smooth_norms_kernel(
+    const float* __restrict__ g, float* __restrict__ gs, const float* __restrict__ taps, int K,
+    float* __restrict__ part, int C, int H, int W, int tiles_x, int tiles_y,
+    int* __restrict__ nonfinite) {
+  extern __shared__ __attribute__((aligned(16))) float ti_lds[];
+  const TiGeom q(K);
+  const int r = q.r, rl = q.rl, HA = q.HA, WA = q.WA, SA = q.SA;
+  float* __restrict__ A = ti_lds + TI_OFFA;
+  float* __restrict__ B = ti_lds + q.offB;
+  const int t = threadIdx.x, n = blockIdx.y;
+  const int tiles = tiles_x * tiles_y;
+  const int c = blockIdx.x / tiles, tile = blockIdx.x - c * tiles;
+  const int ty0 = (tile / tiles_x) * TI_T, tx0 = (tile % tiles_x) * TI_T;
+  const int64_t pbase = ((int64_t)n * C + c) * ((int64_t)H * W);
+  const float* __restrict__ gp = g + pbase;
+
+  if (t < TI_OFFA) ti_lds[t] = t >= 3 && t - 3 < K ? taps[t - 3] : 0.f;
+  if (V == 4) {
+    // 32 consecutive items = 4 rows × 8 vectors: conflict-free dword stores at the odd stride
+    const int NC = WA >> 2, NCB = (NC + 7) >> 3, items = ((HA + 3) >> 2) * NCB * 32;
+#pragma unroll 2
+    for (int i = t; i < items; i += TPB) {
+      const int l = i & 31, b = i >> 5;
+      const int cc = (b % NCB) * 8 + (l & 7), row = (b / NCB) * 4 + (l >> 3);
+      if (cc < NC && row < HA) {
+        const int gy = ty0 - r + row, gx = tx0 - rl + 4 * cc;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *(const f32x4*)(gp + gy * W + gx);
+        float* a = A + row * SA + 4 * cc;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[e] = v[e];
+      }
+    }
+  } else {
+    for (int i = t; i < HA * WA; i += TPB) {
+      const int row = i / WA, col = i - row * WA;
+      const int gy = ty0 - r + row, gx = tx0 - rl + col;
+      A[row * SA + col] = gy >= 0 && gy < H && gx >= 0 && gx < W ? gp[gy * W + gx] : 0.f;
+    }
+  }
+  __syncthreads();
+
+  // horizontal pass: 4 adjacent outputs of one row of A per thread
+  {
+    const int lane = t & 63, wv = t >> 6;
+    const int xg = (lane & 7) + 8 * (wv & 1);
+    for (int row = (lane >> 3) + 8 * (wv >> 1); row < HA; row += 16) {
+      float h[4];
+      ti_filter<float>(A + row * SA + (rl - r) + 4 * xg, 1, ti_lds, K, h);
+      const f32x4 o4 = {h[0], h[1], h[2], h[3]};
+      *(f32x4*)(B + row * TI_T + 4 * xg) = o4;
+    }
+  }
+  __syncthreads();
+
+  // vertical pass: a 4 × 4 patch per thread down 4 columns of B, the same tap order
+  const int x4 = (t & 15) * 4, y0 = (t >> 4) * 4;
+  f32x4 acc[4];
+  ti_filter<f32x4>(B + y0 * TI_T + x4, TI_T, ti_lds, K, acc);
+
+  float s1 = 0.f, s2 = 0.f;
+  bool bad = false;
+  float* __restrict__ op = gs + pbase;
+  const int gx = tx0 + x4;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    const int gy = ty0 + y0 + o;
+    if (gy >= H) break;
+    if (V == 4) {
+      if (gx < W) {  // W % 4 == 0: the vector is whole
+        *(f32x4*)(op + gy * W + gx) = acc[o];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = acc[o][e];
+          bad |= !__builtin_isfinite(v);
+          s1 += fabsf(v);
+          s2 = fmaf(v, v, s2);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (gx + e < W) {
+          const float v = acc[o][e];
+          op[gy * W + gx + e] = v;
+          bad |= !__builtin_isfinite(v);
+          s1 += fabsf(v);
+          s2 = fmaf(v, v, s2);
+        }
+    }
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+  block_slot_store<2>(s1, s2, part);
+}
+
 // ---- C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1, 1]:
 // adv = tanh(w) (= 2·½(tanh w + 1) − 1), w0 = atanh(x) with x clamped to ±(1 − 2⁻²⁰) so that
 // saturated pixels stay finite.
@@ -1688,6 +1870,38 @@ extern "C" int mia_mi_update(float* x, const float* x0, const float* g, const fl
                nonfinite);
   MIA_LAUNCH(mi_update_kernel<1>, grid, dim3(TPB), 0, x, x0, g, l1, m, plane, mu, a, e, lo, hi,
              nonfinite);
+}
+
+extern "C" int mia_ti_smooth_norms(const float* g, float* gs, const float* taps, int K, float* l1,
+                                   float* l2sq, int N, int C, int H, int W, int* nonfinite,
+                                   void* stream) {
+  MIA_CHECK_ARG(g && gs && taps, "null g / gs / taps");
+  MIA_CHECK_ARG(g != gs, "g and gs must be distinct buffers");
+  MIA_CHECK_ARG(K >= 1 && K <= TI_MAXK && (K & 1), "K must be odd, in 1 … 63");
+  MIA_CHECK_ARG(C > 0 && H > 0 && W > 0, "C, H and W must be > 0");
+  const int64_t hw = (int64_t)H * W;  // < 2^62
+  MIA_CHECK_ARG(hw < (1LL << 31), "C·H·W must be below 2^31");
+  const int64_t plane = (int64_t)C * hw;
+  MIA_CHECK_IMAGES(N, plane);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = W % 4 == 0 && aligned16(g) && aligned16(gs);
+  const int tiles_x = (W + TI_T - 1) / TI_T, tiles_y = (H + TI_T - 1) / TI_T;
+  const dim3 grid(C * tiles_x * tiles_y, N);  // ≤ plane < 2^31 blocks per row
+  const void* fn = vec ? (const void*)ti_smooth_norms_kernel<4>
+                       : (const void*)ti_smooth_norms_kernel<1>;
+  if (const int rc = ensure_dyn_lds(fn, TiGeom(TI_MAXK).floats * 4); rc != MIA_OK) return rc;
+  const int lds = TiGeom(K).floats * 4;
+  RedQ r;
+  int rc = red_begin(r, l1, l2sq, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  if (vec)
+    hipLaunchKernelGGL(ti_smooth_norms_kernel<4>, grid, dim3(TPB), lds, st, g, gs, taps, K,
+                       r.part, C, H, W, tiles_x, tiles_y, nonfinite);
+  else
+    hipLaunchKernelGGL(ti_smooth_norms_kernel<1>, grid, dim3(TPB), lds, st, g, gs, taps, K,
+                       r.part, C, H, W, tiles_x, tiles_y, nonfinite);
+  rc = check_launch("ti_smooth_norms_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
 }
 
 extern "C" int mia_cw_init(const float* x, float* w, int64_t len, void* stream) {

@@ -52,7 +52,9 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     * fp16 loss-scale overflows are decided job-wide (``pgd.rescale_consensus``, one int32 MAX
       all-reduce per attack run): every shard re-runs at the same λ, and a fatal overflow raises
       FloatingPointError on EVERY rank (an empty-shard rank included) before the all-gather, so
-      no rank is left blocked in the collective."""
+      no rank is left blocked in the collective.
+    * Every other keyword (``norm``, ``momentum``, ``ti_kernel``, ``ti_nsig``, …) is forwarded to
+      ``pgd.attack`` unchanged; the TI smoothing acts per image plane, so it is shard-local."""
     from . import pgd
     group = group if group is not None else dist.group.WORLD
     world = dist.get_world_size(group)

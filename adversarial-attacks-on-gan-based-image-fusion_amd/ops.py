@@ -605,6 +605,29 @@ def mi_update(x, x0, g, l1, m, mu, a, e, lo=-1.0, hi=1.0, nonfinite=None):
     return x
 
 
+def ti_smooth_norms(g, taps, gs, l1, l2sq, nonfinite=None):
+    """gs ← (taps ⊗ taps) ⋆ g per plane, zero padded (the TI-FGSM smoothing), with
+    l1[n] += Σ|gs_n| and l2sq[n] += Σ gs_n² (either may be None) (mia_ti_smooth_norms).
+    g, gs: distinct fp32 (N,C,H,W); taps: K fp32 device values, K odd in 1 … 63."""
+    if g is None or g.dim() != 4 or g.dtype != torch.float32 or g.numel() == 0:
+        raise ValueError("g must be a non-empty fp32 (N,C,H,W) tensor")
+    N, C, H, W = g.shape
+    _need(gs, g.shape, torch.float32, "gs")
+    if gs.data_ptr() == g.data_ptr():
+        raise ValueError("g and gs must be distinct buffers")
+    if taps is None or taps.dim() != 1 or taps.dtype != torch.float32:
+        raise ValueError("taps must be a 1-D fp32 tensor")
+    K = taps.numel()
+    if K % 2 == 0 or not 1 <= K <= 63:
+        raise ValueError("taps must hold an odd number of values, 1 … 63")
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    call("mia_ti_smooth_norms", ptr(g), ptr(gs), ptr(taps), K, ptr(l1), ptr(l2sq), N, C, H, W,
+         ptr(nonfinite), stream())
+    return gs
+
+
 def cw_init(x, w):
     _need(w, x.shape, torch.float32, "w")
     call("mia_cw_init", ptr(x), ptr(w), x.numel(), stream())

@@ -423,56 +423,90 @@ class AttackEngine:
         ops.grad_assemble_norms(x, self.x0, g_xv, g_enc, g, l1, l2sq, self.pf, ENC_POOL_RES,
                                 self.c_img_o, 1.0 / self.loss_scale, nonfinite=self.nonfinite)
 
-    def step_l2(self, x, a, e):
-        """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units."""
+    def _ti_grad_norms(self, x, taps, l1, l2sq):
+        """The translation-invariant gradient: ∇_x L at x (unscaled, as _grad_norms) smoothed per
+        plane with taps ⊗ taps (ops.ti_smooth_norms), and the per-image Σ|·| / Σ·² of the
+        SMOOTHED gradient. Returns the smoothed gradient (workspace buffer g.ti)."""
         g = self.ws.get("g.full", x.shape, torch.float32)
+        g_xv, g_enc = self.gradient(x)
+        ops.grad_assemble(x, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
+                          1.0 / self.loss_scale, nonfinite=self.nonfinite)
+        gs = self.ws.get("g.ti", x.shape, torch.float32)
+        return ops.ti_smooth_norms(g, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
+
+    def ti_device_taps(self, taps):
+        """The 1-D taps (ti_gaussian_taps) rounded once to fp32, on the engine's device."""
+        t = torch.as_tensor(taps, dtype=torch.float64).reshape(-1)
+        if t.numel() % 2 == 0 or not 1 <= t.numel() <= 63:
+            raise ValueError("ti_taps must hold an odd number of values, 1 … 63")
+        return t.to(torch.float32).to(self.G.device).contiguous()
+
+    def step_l2(self, x, a, e, ti_taps=None):
+        """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units.
+        ``ti_taps`` (fp32 device taps, ti_device_taps): the step follows the smoothed gradient."""
         sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
-        self._grad_norms(x, g, None, sums[0])  # sums: Σg², Σ(adv − x0)² per image
+        if ti_taps is None:
+            g = self.ws.get("g.full", x.shape, torch.float32)
+            self._grad_norms(x, g, None, sums[0])  # sums: Σg², Σ(adv − x0)² per image
+        else:
+            g = self._ti_grad_norms(x, ti_taps, None, sums[0])
         ops.l2_step(x, self.x0, g, sums[0], sums[1], _f32(a), nonfinite=self.nonfinite)
         ops.l2_project(x, self.x0, sums[1], _f32(e))
         return x
 
-    def step_mi(self, x, m, momentum, a, e):
-        """One momentum iterative FGSM step on x and the momentum buffer m, both in place."""
-        g = self.ws.get("g.full", x.shape, torch.float32)
+    def step_mi(self, x, m, momentum, a, e, ti_taps=None):
+        """One momentum iterative FGSM step on x and the momentum buffer m, both in place.
+        ``ti_taps`` (fp32 device taps, ti_device_taps): the TI-FGSM step, on the smoothed
+        gradient and its mean."""
         l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
-        self._grad_norms(x, g, l1, None)
+        if ti_taps is None:
+            g = self.ws.get("g.full", x.shape, torch.float32)
+            self._grad_norms(x, g, l1, None)
+        else:
+            g = self._ti_grad_norms(x, ti_taps, l1, None)
         ops.mi_update(x, self.x0, g, l1, m, _f32(momentum), _f32(a), _f32(e),
                       nonfinite=self.nonfinite)
         return x
 
-    def run_l2(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None):
+    def run_l2(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None,
+               ti_taps=None):
         """L2-ball PGD (torchattacks PGDL2.forward) descending L: per image
         x ← x + a·(−g)/(‖g‖₂ + 1e-10); d = x − x0; x ← clamp(x0 + d·min(e/‖d‖₂, 1), −1, 1), with
         e = 2·eps, a = 2·alpha. ``start_noise``: make_start_noise(shape, seed, "l2"). The norms
-        stay on the device (ordered reductions): no per-step host synchronisation."""
+        stay on the device (ordered reductions): no per-step host synchronisation.
+        ``ti_taps`` (1-D taps, ti_gaussian_taps): g is replaced by (taps ⊗ taps) ⋆ g."""
+        taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         return self._with_rescale(
-            lambda: self._run_l2(x0, t, steps, eps, alpha, random_start, start_noise), group)
+            lambda: self._run_l2(x0, t, steps, eps, alpha, random_start, start_noise, taps),
+            group)
 
-    def _run_l2(self, x0, t, steps, eps, alpha, random_start, start_noise):
+    def _run_l2(self, x0, t, steps, eps, alpha, random_start, start_noise, ti_taps=None):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
         for _ in range(steps):
-            self.step_l2(x, a, e)
+            self.step_l2(x, a, e, ti_taps)
         return x.clone()
 
     def run_mi(self, x0, t, steps, eps, alpha, momentum=1.0, random_start=False, start_noise=None,
-               group=None):
+               group=None, ti_taps=None):
         """Momentum iterative FGSM (torchattacks MIFGSM.forward) descending L: per image
         ĝ = (−g)/mean|g|; m ← ĝ + μ·m (m = 0 at the start);
         x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1), with e = 2·eps, a = 2·alpha.
         An image whose gradient is all zero (0/0) is reported like an overflow, never left frozen
-        silently."""
+        silently. ``ti_taps`` (1-D taps, ti_gaussian_taps): torchattacks TIFGSM without input
+        diversity, g replaced by (taps ⊗ taps) ⋆ g before the normalisation."""
+        taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         return self._with_rescale(
-            lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise),
-            group)
+            lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise,
+                                 taps), group)
 
-    def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise):
+    def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise,
+                ti_taps=None):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
         m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
         for _ in range(steps):
-            self.step_mi(x, m, momentum, a, e)
+            self.step_mi(x, m, momentum, a, e, ti_taps)
         return x.clone()
 
 
@@ -486,6 +520,24 @@ def _check_images(imgs, size, name):
 
 
 NORMS = ("linf", "l2", "adam", "l2_cw")
+TI_MAX_KERNEL = 63  # mia_ti_smooth_norms
+
+
+def ti_gaussian_taps(kernlen=15, nsig=3.0):
+    """The 1-D taps of torchattacks TIFGSM's Gaussian kernel, fp64: k/Σk with k = exp(−x²/2) on
+    linspace(−nsig, nsig, kernlen). torchattacks' gkern (scipy.stats.norm.pdf, whose 1/√(2π)
+    cancels in the normalisation) is exactly outer(taps, taps). The taps are symmetric bit for
+    bit: linspace's two halves can differ by an ulp, so k is averaged with its mirror image."""
+    if (isinstance(kernlen, bool) or not isinstance(kernlen, (int, np.integer))
+            or kernlen % 2 == 0 or not 1 <= kernlen <= TI_MAX_KERNEL):
+        raise ValueError(f"the TI kernel length must be an odd integer in 1 … {TI_MAX_KERNEL}")
+    nsig = float(nsig)
+    if not (np.isfinite(nsig) and nsig > 0):
+        raise ValueError("ti_nsig must be finite and > 0")
+    x = np.linspace(-nsig, nsig, int(kernlen))
+    k = np.exp(-0.5 * x * x)
+    k = 0.5 * (k + k[::-1])
+    return torch.from_numpy(k / k.sum())
 
 
 def make_start_noise(shape, seed, norm="linf"):
@@ -510,7 +562,7 @@ def make_start_noise(shape, seed, norm="linf"):
 
 def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_start=False,
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
-           lr=0.01, cw_c=1e-4, return_info=False, group=None):
+           lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -542,6 +594,16 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                       x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1)
             (AttackEngine.run_mi; torchattacks' default decay is 1.0). An image whose gradient
             is entirely zero raises FloatingPointError instead of staying frozen.
+    ti_kernel  None (default): no smoothing. An odd integer K in 1 … 63, with norm='linf' or 'l2':
+            the translation-invariant attack, the pixel gradient smoothed per plane by the
+            K × K Gaussian W = outer(w, w), w = ti_gaussian_taps(K, ti_nsig) (zero padded, on
+            the fused HIP blur). norm='linf' is the torchattacks TIFGSM rule with
+            diversity_prob = 0 (momentum=None means μ = 0, torchattacks' default decay):
+                      ĝ = W ⋆ (−∇L); ĝ ← ĝ / mean|ĝ|; m ← ĝ + μ·m;
+                      x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1)
+            norm='l2' takes the PGDL2 step above along W ⋆ ∇L and its L2 norm
+            (AttackEngine.run_mi / run_l2 with ti_taps).
+    ti_nsig  the Gaussian's half-width in standard deviations (torchattacks' nsig, 3).
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
     Returns the adversarial images on the input's device (fp32), and a dict if return_info.
@@ -553,6 +615,11 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             raise ValueError("momentum (MI-FGSM) is implemented for norm='linf' only")
         if not float(momentum) >= 0:
             raise ValueError("momentum must be >= 0")
+    ti_taps = None
+    if ti_kernel is not None:
+        if norm not in ("linf", "l2"):
+            raise ValueError("ti_kernel (TI-FGSM) is implemented for norm='linf' and 'l2' only")
+        ti_taps = ti_gaussian_taps(ti_kernel, ti_nsig)
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
@@ -594,15 +661,16 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf" and momentum is not None:
-        adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha), float(momentum),
-                         random_start, noise, group=group)
+    if norm == "linf" and (momentum is not None or ti_taps is not None):
+        adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
+                         float(momentum) if momentum is not None else 0.0, random_start, noise,
+                         group=group, ti_taps=ti_taps)
     elif norm == "linf":
         adv = eng.run(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
                       group=group)
     elif norm == "l2":
         adv = eng.run_l2(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
-                         group=group)
+                         group=group, ti_taps=ti_taps)
     elif norm == "adam":
         adv = eng.run_adam(x0, t, int(steps), lr=float(lr), group=group)
     else:
@@ -610,8 +678,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     adv = adv.to(imgs.device)
     if return_info:
         info = dict(loss=eng.loss(adv.to(dev)), steps=int(steps), eps=eps, alpha=alpha, norm=norm,
-                    momentum=momentum, dtype=str(eng.dtype), loss_scale=eng.loss_scale,
-                    rescales=eng.rescales)
+                    momentum=momentum, ti_kernel=ti_kernel, dtype=str(eng.dtype),
+                    loss_scale=eng.loss_scale, rescales=eng.rescales)
         return adv, info
     return adv
 

@@ -422,6 +422,21 @@ int mia_l2_project(float* x, const float* x0, const float* dsq, int N, int64_t p
 int mia_mi_update(float* x, const float* x0, const float* g, const float* l1, float* m, int N,
                   int64_t plane, float mu, float a, float e, float lo, float hi, int* nonfinite,
                   void* stream);
+/* Translation-invariant smoothing of a gradient (torchattacks TIFGSM: the depth-wise Gaussian
+ * over the pixel gradient) with the per-image norms of the result, in one pass:
+ *   gs[n,c] = (taps ⊗ taps) ⋆ g[n,c]   zero padded, F.conv2d(padding="same", groups=C),
+ *   l1[n] += Σ|gs_n|,  l2sq[n] += Σ gs_n²   (fp32 [N], either may be NULL; ordered reductions
+ *   as in mia_grad_assemble_norms: one partial per 64 × 64 tile of each plane).
+ * g, gs: fp32 (N,C,H,W), distinct buffers; taps: K fp32 values in device memory, K odd in
+ * 1 … 63; any H, W ≥ 1. The filter runs separably (rows, then columns), each output as
+ * t[0]·v[0] followed by fma(t[k], v[k], ·) in tap order: an element's value depends on its plane
+ * and position only, so reruns are bit-identical and an image's gs and sums do not depend on the
+ * other images of the call; K = 1 with taps = {1} returns g bit for bit. W % 4 == 0 with 16-byte
+ * aligned g / gs moves 16-byte vectors, anything else scalars (the same bits either way).
+ * nonfinite (NULL or int[N]) is set for an image with a non-finite element of gs. The sums feed
+ * mia_mi_update / mia_l2_step from device memory. */
+int mia_ti_smooth_norms(const float* g, float* gs, const float* taps, int K, float* l1,
+                        float* l2sq, int N, int C, int H, int W, int* nonfinite, void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);

@@ -135,6 +135,19 @@ int main() {
                              1.f, nullptr, nullptr), "mi_update mu");
   expect_error(mia_mi_update(dummy, dummy, dummy, dummy, dummy, 1 << 20, 3072, 1.f, 0.1f, 0.1f,
                              -1.f, 1.f, nullptr, nullptr), "mi_update N");
+  // the translation-invariant blur: null / in-place buffers, kernel lengths, sizes that overflow
+  expect_error(mia_ti_smooth_norms(dummy, dummy + 32, nullptr, 15, dummy, dummy, 2, 3, 32, 32,
+                                   nullptr, nullptr), "ti_smooth_norms null taps");
+  expect_error(mia_ti_smooth_norms(dummy, dummy, dummy, 15, dummy, dummy, 2, 3, 32, 32, nullptr,
+                                   nullptr), "ti_smooth_norms in place");
+  expect_error(mia_ti_smooth_norms(dummy, dummy + 32, dummy, 14, dummy, dummy, 2, 3, 32, 32,
+                                   nullptr, nullptr), "ti_smooth_norms even K");
+  expect_error(mia_ti_smooth_norms(dummy, dummy + 32, dummy, 65, dummy, dummy, 2, 3, 32, 32,
+                                   nullptr, nullptr), "ti_smooth_norms K > 63");
+  expect_error(mia_ti_smooth_norms(dummy, dummy + 32, dummy, 15, dummy, dummy, 2, 3, 1 << 30,
+                                   1 << 30, nullptr, nullptr), "ti_smooth_norms H*W overflow");
+  expect_error(mia_ti_smooth_norms(dummy, dummy + 32, dummy, 15, dummy, dummy, 1 << 20, 3, 32, 32,
+                                   nullptr, nullptr), "ti_smooth_norms N");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
