@@ -1740,9 +1740,23 @@ extern "C" int mia_mse_fwd_bwd(const void* a, const void* b, float* loss, void* 
   return mia_tap_grad(a, b, g, (int64_t)n * len, coef_grad, 0, dtype, stream);
 }
 
+// The shape checks of the launchers that read the pooled gradients per image element
+// (image_grad / pgd_update / grad_assemble; mia_grad_assemble_norms makes the same ones): the
+// kernels index g_vgg as [n][y / pf][x / pf][c < 3] of cpad channels and g_enc as
+// [n][c][y / (S / enc_res)][x / (S / enc_res)].
+#define MIA_CHECK_PIXEL_GRAD(N, S, pf, cpad, g_vgg, g_enc, enc_res, dtype)                      \
+  MIA_CHECK_ARG((S) > 0 && (S) <= 16384, "S must be in 1 … 16384");                             \
+  MIA_CHECK_ARG((N) > 0 && (N) <= 65535, "N must be in 1 … 65535");                             \
+  MIA_CHECK_ARG((pf) >= 1 && (S) % (pf) == 0, "pf must divide S");                              \
+  MIA_CHECK_ARG(!(g_vgg) || (cpad) >= 3, "cpad must be >= 3");                                  \
+  MIA_CHECK_ARG(!(g_enc) || ((enc_res) >= 1 && (S) % (enc_res) == 0), "enc_res must divide S"); \
+  MIA_CHECK_ARG((dtype) == MIA_F32 || (dtype) == MIA_F16 || (dtype) == MIA_BF16,                \
+                "unsupported dtype")
+
 extern "C" int mia_image_grad(const float* rec, const float* t, const void* g_vgg, float* g_img,
                               int N, int S, int pf, int cpad, float coef, int dtype, void* stream) {
-  MIA_CHECK_ARG(rec && t && g_img && pf >= 1 && S % pf == 0, "bad args");
+  MIA_CHECK_ARG(rec && t && g_img, "null rec / t / g_img");
+  MIA_CHECK_PIXEL_GRAD(N, S, pf, cpad, g_vgg, (const float*)nullptr, S, dtype);
   const int64_t total = (int64_t)N * 3 * S * S;
   MIA_DISPATCH_DTYPE(dtype, T,
       MIA_LAUNCH(image_grad_kernel<T>, dim3(blocks_for(total, TPB, 65536)), dim3(TPB), 0, rec, t,
@@ -1754,7 +1768,10 @@ extern "C" int mia_pgd_update(float* x, const float* x0, const void* g_vgg, cons
                               int N, int S, int pf, int cpad, int enc_res, float coef_img, float a,
                               float e, float lo, float hi, int* nonfinite, int dtype,
                               void* stream) {
-  MIA_CHECK_ARG(x && x0 && pf >= 1 && S % pf == 0 && enc_res >= 1 && S % enc_res == 0, "bad args");
+  MIA_CHECK_ARG(x && x0, "null x / x0");
+  MIA_CHECK_ARG(lo <= hi, "need lo <= hi");
+  MIA_CHECK_PIXEL_GRAD(N, S, pf, cpad, g_vgg, g_enc, enc_res, dtype);
+  if (!g_enc) enc_res = S;  // unused, but the kernel divides by S / enc_res
   const int64_t total = (int64_t)N * 3 * S * S;
   MIA_DISPATCH_DTYPE(dtype, T,
       MIA_LAUNCH(pgd_update_kernel<T>, dim3(blocks_for(total, TPB, 65536)), dim3(TPB), 0, x, x0,
@@ -1767,7 +1784,9 @@ extern "C" int mia_grad_assemble(const float* x, const float* x0, const void* g_
                                  const float* g_enc, float* g, int N, int S, int pf, int cpad,
                                  int enc_res, float coef_img, float scale, int* nonfinite,
                                  int dtype, void* stream) {
-  MIA_CHECK_ARG(x && x0 && g && pf >= 1 && S % pf == 0 && (!g_enc || S % enc_res == 0), "bad args");
+  MIA_CHECK_ARG(x && x0 && g, "null x / x0 / g");
+  MIA_CHECK_PIXEL_GRAD(N, S, pf, cpad, g_vgg, g_enc, enc_res, dtype);
+  if (!g_enc) enc_res = S;  // unused, but the kernel divides by S / enc_res
   const int64_t total = (int64_t)N * 3 * S * S;
   MIA_DISPATCH_DTYPE(dtype, T,
       MIA_LAUNCH(grad_assemble_kernel<T>, dim3(blocks_for(total, TPB, 65536)), dim3(TPB), 0, x,

@@ -481,14 +481,27 @@ def tap_grad(a, t, g, coef, mask=True):
     return g
 
 
-def image_grad(rec, t, g_vgg, g_img, pf, coef):
-    N, _, S, _ = rec.shape
-    _need(t, rec.shape, torch.float32, "t")
-    _need(g_img, rec.shape, torch.float32, "g_img")
+def _pixel_grad_shape(x, g_vgg, pf, name="x"):
+    """(N, S, cpad) of an (N,3,S,S) fp32 image batch and its pooled NHWC gradient g_vgg (or None),
+    whose first three of cpad channels the kernels read."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.dtype != torch.float32:
+        raise ValueError(f"{name} must be (N,3,S,S) fp32")
+    N, _, S, _ = x.shape
+    if pf < 1 or S % pf:
+        raise ValueError("pf must divide S")
     cpad = 8
     if g_vgg is not None:
-        _need(g_vgg, (N, S // pf, S // pf, g_vgg.shape[-1]), None, "g_vgg")
         cpad = g_vgg.shape[-1]
+        if cpad < 3:
+            raise ValueError(f"g_vgg: {cpad} channels, at least 3 are read")
+        _need(g_vgg, (N, S // pf, S // pf, cpad), None, "g_vgg")
+    return N, S, cpad
+
+
+def image_grad(rec, t, g_vgg, g_img, pf, coef):
+    N, S, cpad = _pixel_grad_shape(rec, g_vgg, pf, "rec")
+    _need(t, rec.shape, torch.float32, "t")
+    _need(g_img, rec.shape, torch.float32, "g_img")
     gdt = dt(g_vgg) if g_vgg is not None else _lib.MIA_F32
     call("mia_image_grad", ptr(rec), ptr(t), ptr(g_vgg), ptr(g_img), N, S, pf, cpad, float(coef),
          gdt, stream())
@@ -497,13 +510,9 @@ def image_grad(rec, t, g_vgg, g_img, pf, coef):
 
 def pgd_update(x, x0, g_vgg, g_enc, pf, enc_res, coef_img, a, e, lo=-1.0, hi=1.0,
                nonfinite=None):
-    N, _, S, _ = x.shape
+    N, S, cpad = _pixel_grad_shape(x, g_vgg, pf)
     _numel_ok(nonfinite, N, torch.int32, "nonfinite")
     _need(x0, x.shape, torch.float32, "x0")
-    cpad = 8
-    if g_vgg is not None:
-        _need(g_vgg, (N, S // pf, S // pf, g_vgg.shape[-1]), None, "g_vgg")
-        cpad = g_vgg.shape[-1]
     if g_enc is not None:
         _numel_ok(g_enc, N * 3 * enc_res * enc_res, torch.float32, "g_enc")
     gdt = dt(g_vgg) if g_vgg is not None else _lib.MIA_F32

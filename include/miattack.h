@@ -373,7 +373,11 @@ int mia_image_grad(const float* rec, const float* t, const void* g_vgg, float* g
  *   adv = x + a·sign(−g); δ = clamp(adv − x0, −e, e); x = clamp(x0 + δ, lo, hi)   (in place)
  * g_vgg may be NULL; g_enc may be NULL (else (N,3,enc_res,enc_res) fp32).
  * nonfinite: NULL or int[N]; set to 1 for every image with a non-finite gradient element (an
- * fp16 loss-scale overflow: the host lowers the scale and re-runs). */
+ * fp16 loss-scale overflow: the host lowers the scale and re-runs).
+ * MIA_EINVAL before any launch, here and in mia_grad_assemble / mia_image_grad: a NULL image
+ * buffer, S outside 1 … 16384, N outside 1 … 65535, pf not dividing S, g_vgg with cpad < 3, g_enc
+ * with an enc_res that does not divide S (enc_res is ignored without g_enc), an unknown dtype;
+ * here also lo > hi. */
 int mia_pgd_update(float* x, const float* x0, const void* g_vgg, const float* g_enc, int N,
                    int S, int pf, int cpad, int enc_res, float coef_img, float a, float e,
                    float lo, float hi, int* nonfinite, int dtype, void* stream);

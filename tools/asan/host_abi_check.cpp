@@ -119,6 +119,35 @@ int main() {
   expect_error(mia_grad_assemble_norms(dummy, dummy, nullptr, nullptr, dummy, dummy, dummy, 2, 32,
                                        1, 8, 16, 1.f, 1.f, nullptr, 99, nullptr),
                "grad_assemble_norms dtype");
+  // the L∞ update, the plain assembly and the reconstruction's image gradient: the same checks
+  expect_error(mia_pgd_update(dummy, nullptr, dummy, dummy, 2, 32, 1, 8, 16, 0.37f, 0.03f, 0.06f,
+                              -1.f, 1.f, nullptr, MIA_F32, nullptr), "pgd_update null x0");
+  expect_error(mia_pgd_update(dummy, dummy, dummy, dummy, 2, 32, 1, 2, 16, 0.37f, 0.03f, 0.06f,
+                              -1.f, 1.f, nullptr, MIA_F32, nullptr), "pgd_update cpad");
+  expect_error(mia_pgd_update(dummy, dummy, dummy, dummy, 1 << 16, 32, 1, 8, 16, 0.37f, 0.03f,
+                              0.06f, -1.f, 1.f, nullptr, MIA_F32, nullptr), "pgd_update N");
+  expect_error(mia_pgd_update(dummy, dummy, dummy, dummy, 2, 32, 1, 8, 0, 0.37f, 0.03f, 0.06f,
+                              -1.f, 1.f, nullptr, MIA_F32, nullptr), "pgd_update enc_res");
+  expect_error(mia_pgd_update(dummy, dummy, dummy, dummy, 2, 32, 1, 8, 16, 0.37f, 0.03f, 0.06f,
+                              1.f, -1.f, nullptr, MIA_F32, nullptr), "pgd_update lo > hi");
+  expect_error(mia_grad_assemble(dummy, dummy, dummy, dummy, nullptr, 2, 32, 1, 8, 16, 0.37f, 1.f,
+                                 nullptr, MIA_F32, nullptr), "grad_assemble null g");
+  expect_error(mia_grad_assemble(dummy, dummy, dummy, dummy, dummy, 2, 32, 1, 1, 16, 0.37f, 1.f,
+                                 nullptr, MIA_F16, nullptr), "grad_assemble cpad");
+  expect_error(mia_grad_assemble(dummy, dummy, dummy, dummy, dummy, 2, 32, 1, 8, 0, 0.37f, 1.f,
+                                 nullptr, MIA_F32, nullptr), "grad_assemble enc_res 0");
+  expect_error(mia_grad_assemble(dummy, dummy, dummy, dummy, dummy, 2, 20000, 1, 8, 16, 0.37f,
+                                 1.f, nullptr, MIA_F32, nullptr), "grad_assemble S");
+  expect_error(mia_image_grad(dummy, dummy, dummy, nullptr, 2, 32, 1, 8, 0.37f, MIA_F32, nullptr),
+               "image_grad null g_img");
+  expect_error(mia_image_grad(dummy, dummy, dummy, dummy, 2, 32, 3, 8, 0.37f, MIA_F32, nullptr),
+               "image_grad pf");
+  expect_error(mia_image_grad(dummy, dummy, dummy, dummy, 2, 32, 1, 2, 0.37f, MIA_BF16, nullptr),
+               "image_grad cpad");
+  expect_error(mia_image_grad(dummy, dummy, dummy, dummy, 0, 32, 1, 8, 0.37f, MIA_F32, nullptr),
+               "image_grad N");
+  expect_error(mia_image_grad(dummy, dummy, nullptr, dummy, 2, 32, 1, 8, 0.37f, 99, nullptr),
+               "image_grad dtype");
   expect_error(mia_l2_step(dummy, dummy, dummy, nullptr, dummy, 2, 3072, 0.1f, nullptr, nullptr),
                "l2_step null norm");
   expect_error(mia_l2_step(dummy, dummy, dummy, dummy, dummy, -1, 3072, 0.1f, nullptr, nullptr),
