@@ -34,6 +34,11 @@
 // tile), a persistent form, and (round 3) per-stage LDS counters instead of the per-step block
 // barrier (B-waves refill a stage once all 8 waves have read it, readers start once its 4 pieces
 // landed, barriers only at channel-block ends): step 7564 → 7568 ms, ±3 % per layer.
+// Round 7, what did move it (STG, the 128-column tile): waves 4–7 run their MFMAs one half-step
+// late on fragments kept in registers, so the two waves of a SIMD alternate matrix pipe and LDS
+// instead of reaching each together — K-step 4207 → 3880 cycles, bit-identical.
+#include <type_traits>
+
 #include "conv_common.h"
 #include "halo_epilogue.h"
 
@@ -44,7 +49,9 @@ namespace mia {
 // adds its phase cycles here; nothing in the kernel reads them back and no output depends on them.
 // [variant = (BN == 128) + 2·PRO][blocks, cycles, prologue, in-loop splits, epilogue, 100-MHz
 // ticks, K-steps, wave 0 (weights) / wave 4 (halo) cycles in the end-of-step wait + barrier, -…]
-__device__ unsigned long long g_x6_stamps[4][16];
+// [9…12] wave 0, [13…16] wave 4 (its SIMD partner), summed over the K-steps from the step's top
+// (barrier release): start of the fragment reads, first MFMA, arrival at the step-end wait, release.
+__device__ unsigned long long g_x6_stamps[4][24];
 #endif
 
 // BN_ = 128: 4 row waves × 2 column waves of 4 × 4 fragments; BN_ = 64 (the 64-channel layers):
@@ -77,10 +84,11 @@ struct HaloX6 {
   static_assert(LDS <= 160 * 1024, "");
 };
 
-template <int BN_, bool PRO, int EPI, bool EARLY, bool PRIO, bool UNR, int TPS = 1>
+template <int BN_, bool PRO, int EPI, bool EARLY, bool PRIO, bool UNR, int TPS = 1, int STG = 0>
 __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const ConvK k) {
   static_assert(!UNR || (EARLY && PRIO && EPI != -2), "UNR: the EARLY + PRIO schedule, D[ch][px]");
   static_assert(UNR || TPS == 1, "several taps per K-step: the unrolled loop only");
+  static_assert(STG == 0 || (UNR && TPS == 1 && BN_ == 128), "staggered loop: the 128-column tile");
   typedef HaloX6<BN_, TPS> TL;
   constexpr int NG = TL::NG;
   constexpr int FM = TL::FM, FN = TL::FN, WN = TL::WN, NT = TL::NT, BN = TL::BN, BK = TL::BK;
@@ -117,6 +125,7 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
   const unsigned long long st_t0 = __builtin_amdgcn_s_memtime();
   const unsigned long long st_r0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long st_pro = 0, st_cv = 0, st_wb = 0;
+  unsigned long long st_rd = 0, st_m0 = 0, st_arr = 0, st_rel = 0;
 #endif
 
   // per-lane DMA sources (byte pointers; nullptr → the zero page)
@@ -248,6 +257,136 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
         ol[q][c] = vl;
       }
     int st = 0;
+    if constexpr (STG != 0) {
+      // The staggered loop: the two waves of a SIMD (w and w + 4) run the same half-steps
+      // (fragment reads, then 48 MFMAs) in opposite phase. Waves 0–3 lead: reads(k), MFMAs(k).
+      // Waves 4–7 lag by the MFMA half only: their interval is MFMAs(k − 1) on the fragments they
+      // read in the previous interval and kept in registers, then reads(k) — so after every
+      // barrier one partner opens on the matrix pipe and the other on LDS. The lagging half skips
+      // the MFMAs of the very first interval and runs those of the last half-step after the loop;
+      // every wave passes the same barriers. Each wave's MFMAs and their order are those of the
+      // loop below: bit-identical outputs.
+      // Buffer lifetimes are the unstaggered loop's: every wave still READS half-step k between
+      // barriers k − 1 and k; only the lagging MFMAs, which touch registers alone, cross a barrier.
+      // One copy of the loop per half (a wave-uniform branch): each is straight-line code like the
+      // loop below, so the carried fragments cost no copies or spills.
+      auto loop = [&](auto lagc) {
+      constexpr bool lag = decltype(lagc)::value;
+      u32x4 ahm[FM], bhm[FN];  // the lagging half carries these across the barriers
+      u32x2 al[FM], blo[FN];
+      auto mfmas = [&] {
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j)
+            acc[i][j] = mfma_x6(bhm[j], blo[j], ahm[i], al[i], acc[i][j]);  // D[ch][px]
+        __builtin_amdgcn_s_setprio(0);
+      };
+      for (int cb = 0; cb < ncb; ++cb) {
+#pragma unroll
+        for (int tg = 0; tg < NG; ++tg) {
+          const int s = cb * NG + tg;
+          int hoff = (cb & 1) * HBUF, x1 = 64, x2 = 32;  // opaque per step, as below
+          asm volatile("" : "+s"(hoff), "+s"(x1), "+s"(x2));
+          const char* ha = hbuf + hoff;
+          const char* sb = bring + st * BSTAGE;
+          const int dy = tg / 3, dx = tg % 3;
+#ifdef MIA_STAMPS
+          const unsigned long long t_top = __builtin_amdgcn_s_memtime();
+          unsigned long long t_rd = 0, t_m0 = 0;
+#endif
+          // Weight stage st ^ 1 held step s − 1: its last reads (h = 1, every wave) retired before
+          // the barrier that ended step s − 1; this DMA is waited for (vmcnt(0), waves 0–3) before
+          // the barrier that ends step s, after which step s + 1 reads it.
+          if (!lag && s + 1 < nk) issue_b(s + 1, st ^ 1);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            auto reads = [&] {
+              const int ch = h * 4 + fq;
+#pragma unroll
+              for (int i = 0; i < FM; ++i) {
+                ahm[i] = *(const u32x4*)(ha + (h ? oh[i + dy][dx] ^ x1 : oh[i + dy][dx]));
+                al[i] = *(const u32x2*)(lbuf + (h ? ol[i + dy][dx] ^ x2 : ol[i + dy][dx]));
+              }
+#pragma unroll
+              for (int j = 0; j < FN; ++j) {
+                const int row = wn * FN * 16 + 16 * j + frow;
+                bhm[j] = *(const u32x4*)(sb + row * ROWB + ((ch ^ fsw(row)) << 4));
+                blo[j] = *(const u32x2*)(sb + TL::BHM + row * TL::LROWB + ((ch ^ lsw(row)) << 3));
+              }
+            };
+            if constexpr (!lag) {
+#ifdef MIA_STAMPS
+              if (h == 0) t_rd = __builtin_amdgcn_s_memtime();
+#endif
+              reads();
+            }
+#ifdef MIA_STAMPS
+            if (h == 0) t_m0 = __builtin_amdgcn_s_memtime();
+#endif
+            if (tg == 0 && h == 0) {
+              if (!(lag && cb == 0)) mfmas();  // lagging half: nothing read yet in the first interval
+            } else {
+              mfmas();
+            }
+            if constexpr (lag) {
+              // Halo buffer (cb + 1) & 1 held block cb − 1, last read before the barrier that ended
+              // its last step; the DMA is waited for (vmcnt(0), waves 4–7) before the barrier that
+              // ends this block's last step, after which convert() reads it. Issued in the lagging
+              // wave's non-MFMA part.
+              if (h == 0 && cb + 1 < ncb && tg < (H_INS + HPS - 1) / HPS) {
+#pragma unroll
+                for (int q = 0; q < HPS; ++q) {
+                  const int j = tg * HPS + q;
+                  if (j < H_INS && j < my_pieces) issue_h(cb + 1, j, (cb + 1) & 1);
+                }
+              }
+#ifdef MIA_STAMPS
+              if (h == 0) t_rd = __builtin_amdgcn_s_memtime();
+#endif
+              reads();
+            }
+          }
+#ifdef MIA_STAMPS
+          const unsigned long long w0 = __builtin_amdgcn_s_memtime();
+#endif
+          if (!lag || tg == NG - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          // Step-end barrier: every wave's LDS reads of step s have returned (lgkmcnt(0); the
+          // lagging half keeps its h = 1 fragments in registers), so stage st may be refilled by
+          // the DMA issued after it, and — on a block's last step — lbuf and halo buffer cb & 1
+          // may be rewritten by convert(cb + 1) and the DMA of block cb + 2.
+          lds_handoff();
+          __builtin_amdgcn_sched_barrier(0);
+#ifdef MIA_STAMPS
+          {
+            const unsigned long long t_end = __builtin_amdgcn_s_memtime();
+            st_wb += t_end - w0;
+            st_rd += t_rd - t_top;
+            st_m0 += t_m0 - t_top;
+            st_arr += w0 - t_top;
+            st_rel += t_end - t_top;
+          }
+#endif
+          if (tg == NG - 1 && cb + 1 < ncb) {
+#ifdef MIA_STAMPS
+            const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+#endif
+            convert(cb + 1, (cb + 1) & 1);  // the lagging half still holds block cb's last fragments
+            __syncthreads();
+#ifdef MIA_STAMPS
+            st_cv += __builtin_amdgcn_s_memtime() - c0;
+#endif
+          }
+          st ^= 1;
+        }
+      }
+      if constexpr (lag) mfmas();  // the lagging half's last half-step
+      };
+      static_assert(TL::BWAVES == 4, "the weight waves lead, the halo waves lag");
+      if (bwave) loop(std::false_type{});
+      else loop(std::true_type{});
+    } else {
     for (int cb = 0; cb < ncb; ++cb) {
 #pragma unroll
       for (int tg = 0; tg < NG; ++tg) {
@@ -258,6 +397,10 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
         asm volatile("" : "+s"(hoff), "+s"(x1), "+s"(x2));
         const char* ha = hbuf + hoff;
         const char* sb0 = bring + st * BSTAGE;
+#ifdef MIA_STAMPS
+        const unsigned long long t_top = __builtin_amdgcn_s_memtime();
+        unsigned long long t_rd = 0, t_m0 = 0;
+#endif
         if (bwave && s + 1 < nk) issue_b(s + 1, st ^ 1);
         if (!bwave && cb + 1 < ncb && tg < (H_INS + HPS - 1) / HPS) {
 #pragma unroll
@@ -277,6 +420,9 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
             const int ch = h * 4 + fq;
             u32x4 ahm[FM], bhm[FN];
             u32x2 al[FM], blo[FN];
+#ifdef MIA_STAMPS
+            if (tt == 0 && h == 0) t_rd = __builtin_amdgcn_s_memtime();
+#endif
 #pragma unroll
             for (int i = 0; i < FM; ++i) {
               ahm[i] = *(const u32x4*)(ha + (h ? oh[i + dy][dx] ^ x1 : oh[i + dy][dx]));
@@ -289,6 +435,9 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
               blo[j] = *(const u32x2*)(sb + TL::BHM + row * TL::LROWB + ((ch ^ lsw(row)) << 3));
             }
             __builtin_amdgcn_s_setprio(1);
+#ifdef MIA_STAMPS
+            if (tt == 0 && h == 0) t_m0 = __builtin_amdgcn_s_memtime();
+#endif
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -305,7 +454,14 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
 #ifdef MIA_STAMPS
-        st_wb += __builtin_amdgcn_s_memtime() - w0;
+        {
+          const unsigned long long t_end = __builtin_amdgcn_s_memtime();
+          st_wb += t_end - w0;
+          st_rd += t_rd - t_top;
+          st_m0 += t_m0 - t_top;
+          st_arr += w0 - t_top;
+          st_rel += t_end - t_top;
+        }
 #endif
         if (tg == NG - 1 && cb + 1 < ncb) {
 #ifdef MIA_STAMPS
@@ -320,6 +476,7 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
         st ^= 1;
       }
     }
+    }  // STG == 0
   } else {
   int st = 0, cb = 0, t = 0;
   for (int s = 0; s < nk; ++s) {
@@ -439,11 +596,18 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
     atomicAdd(g + 7, st_wb);
   }
   if (wid == 4 && lane == 0) atomicAdd(&g_x6_stamps[(BN_ == 128 ? 1 : 0) + (PRO ? 2 : 0)][8], st_wb);
+  if ((wid == 0 || wid == 4) && lane == 0) {
+    unsigned long long* g = g_x6_stamps[(BN_ == 128 ? 1 : 0) + (PRO ? 2 : 0)] + (wid ? 13 : 9);
+    atomicAdd(g + 0, st_rd);
+    atomicAdd(g + 1, st_m0);
+    atomicAdd(g + 2, st_arr);
+    atomicAdd(g + 3, st_rel);
+  }
 #endif
 }
 
 template <int BN_, bool PRO, int EPI, bool EARLY, bool PRIO = false, bool UNR = false,
-          int TPS = 1>
+          int TPS = 1, int STG = 0>
 static int launch_x6_e(ConvK& k, hipStream_t st) {
   typedef HaloX6<BN_, TPS> TL;
   k.nbn = (k.a.Cout + TL::BN - 1) / TL::BN;
@@ -451,7 +615,7 @@ static int launch_x6_e(ConvK& k, hipStream_t st) {
   size_t lds = TL::LDS;
   lds = std::max(lds, (size_t)TL::EROWS * TL::ES * 4);
   lds = std::max(lds, (size_t)TL::NW * TL::BN * 4);
-  auto fn = conv_halo_x6_kernel<BN_, PRO, EPI, EARLY, PRIO, UNR, TPS>;
+  auto fn = conv_halo_x6_kernel<BN_, PRO, EPI, EARLY, PRIO, UNR, TPS, STG>;
   if (const int rc = ensure_dyn_lds((const void*)fn, 160 * 1024); rc != MIA_OK) return rc;
   k.prered = EPI >= 0 && (EPI & epi::CSUM);
   const int H = k.a.H, W = k.a.W;
@@ -466,6 +630,21 @@ static int launch_x6_e(ConvK& k, hipStream_t st) {
   return rc != MIA_OK ? rc : red_finish(r, st);
 }
 
+// A/B build macro (csrc/Makefile `variant`): MIA_X6_STAGGER_ALL = 0 / 1 routes no / every 128-column
+// launch to the staggered loop.
+// The instantiations routed to the staggered loop: every feature mask measured faster in both
+// alternations of the layer A/B (profiles/r07_x6_stagger_ab.txt), the modulated forward too
+// (2–4 %), but that one (PRO: the in-LDS modulation's operands are live as well) spills 10 VGPRs
+// to scratch at 256 registers, so it stays on the unstaggered loop until it fits.
+constexpr bool x6_stagger_wins(bool pro, int epi) {
+#ifdef MIA_X6_STAGGER_ALL
+  return MIA_X6_STAGGER_ALL != 0;
+#else
+  (void)epi;
+  return !pro;
+#endif
+}
+
 template <int BN_, bool PRO, int EPI>
 static int launch_x6_(ConvK& k, hipStream_t st) {
   // the next block's halo DMA at the step start (measured +2-3 % on the stride-1 layers over
@@ -476,6 +655,13 @@ static int launch_x6_(ConvK& k, hipStream_t st) {
     const int u = tune(T_X6_UNR);
     if constexpr (BN_ == 64) {
       if (u == 2) return launch_x6_e<BN_, PRO, EPI, true, true, true, 2>(k, st);
+    }
+    if constexpr (BN_ == 128) {
+      // T_X6_STAGGER: -1 (default) the per-instantiation choice of the layer A/B
+      // (profiles/r07_x6_stagger_ab.txt), 0 / 1 force the unstaggered / staggered loop (tests, A/B)
+      const int sg = tune(T_X6_STAGGER);
+      if (u != 0 && (sg < 0 ? x6_stagger_wins(PRO, EPI) : sg != 0))
+        return launch_x6_e<BN_, PRO, EPI, true, true, true, 1, 1>(k, st);
     }
     if (u != 0) return launch_x6_e<BN_, PRO, EPI, true, true, true>(k, st);
   }
@@ -807,7 +993,7 @@ extern "C" int mia_debug_x6_stamps(unsigned long long* host, int reset) {
   if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_x6_stamps), sizeof(g_x6_stamps)) != hipSuccess)
     return 1;
   if (reset) {
-    static const unsigned long long zero[4][16] = {};
+    static const unsigned long long zero[4][24] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_x6_stamps), zero, sizeof(zero)) != hipSuccess) return 1;
   }
   return 0;

@@ -608,15 +608,9 @@ template <typename T, bool PRO, int EPI>
 static int launch_wres32_(ConvK& k, hipStream_t st) {
   typedef Wres32Tile TL;
   auto fn = conv_wres32_kernel<T, PRO, EPI>;
-  // blocks per CU of this instantiation (a thread-safe function-local static), × the device's CUs
-  static const int occ = [&] {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)fn, TL::NT, TL::LDS) !=
-            hipSuccess || o < 1)
-      o = 1;
-    return o;
-  }();
-  const int per_cu = device_cu_count() * occ;
+  // blocks per CU of this instantiation on the current device (cached per kernel and device),
+  // × the device's CUs
+  const int per_cu = device_cu_count() * max_blocks_per_cu((const void*)fn, TL::NT, TL::LDS);
   const int ntiles = k.a.N * (k.a.H / TL::PH) * (k.a.W / TL::PW);
   const int grid = std::min(ntiles, per_cu);
   k.nbn = 1;

@@ -76,6 +76,9 @@ int check_launch(const char* what);
 // device) — the launchers' lazy initialisation, safe for several host threads and devices.
 int device_cu_count();
 int ensure_dyn_lds(const void* fn, int bytes);
+// resident blocks per CU of `fn` at this block size and dynamic LDS on the current device (≥ 1),
+// queried once per (kernel, device)
+int max_blocks_per_cu(const void* fn, int threads, size_t dyn_lds);
 
 // Kernel-variant switches (tests' bitwise A/B comparisons and the tuning tools; the product path
 // never changes them): read ONCE from the environment (MIA_<NAME>=value) at first use, then only
@@ -104,6 +107,9 @@ enum TuneKey {
                      // 8 × 16-patch two-blocks-per-CU form (conv_upconv.hip DgX6S), 0 the 8-wave one
   T_CONV_WRES128,    // 0: the 2-byte 128 → 128 StyledConv forward on per-image weights on the
                      // halo tile instead of the weights-resident kernel (conv_wres128.hip)
+  T_X6_STAGGER,      // fp32 x6 halo kernel, 128-column tile: -1 (default) the staggered loop where it
+                     // measured faster, 0 never, 1 always (bitwise tests and A/B tools; set through
+                     // mia_set_tuning only, never read from the environment)
   T_NKEYS
 };
 int tune(TuneKey key);

@@ -36,10 +36,11 @@ TuneDef g_tune[T_NKEYS] = {
     {"MIA_S2DG_X6", 1},   {"MIA_S2DG_HALO", 1},     {"MIA_UPCONV_X6", 1},   {"MIA_UPCONV_HALO", 1},
     {"MIA_CONV_WRES32", 1},
     {"MIA_HALO_C64", 1},  {"MIA_X6_64S", 1},
-    {"MIA_UPCONV_X6S", 1}, {"MIA_CONV_WRES128", 1}};
+    {"MIA_UPCONV_X6S", 1}, {"MIA_CONV_WRES128", 1}, {"MIA_X6_STAGGER", -1}};
 std::once_flag g_tune_once;
 void tune_init() {
   for (auto& d : g_tune) {
+    if (&d == &g_tune[T_X6_STAGGER]) continue;  // mia_set_tuning only
     const char* e = getenv(d.name);
     if (e && *e) d.value = atoi(e);
   }
@@ -84,6 +85,21 @@ int ensure_dyn_lds(const void* fn, int bytes) {
     return set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   done.push_back(dev);
   return MIA_OK;
+}
+
+int max_blocks_per_cu(const void* fn, int threads, size_t dyn_lds) {
+  static std::unordered_map<const void*, std::unordered_map<int, int>> cache;  // kernel → device
+  const int dev = current_device();
+  std::lock_guard<std::mutex> lock(g_dev_mu);
+  auto& per_dev = cache[fn];
+  auto it = per_dev.find(dev);
+  if (it != per_dev.end()) return it->second;
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, dyn_lds) != hipSuccess ||
+      occ < 1)
+    occ = 1;
+  per_dev[dev] = occ;
+  return occ;
 }
 
 float* red_scratch(hipStream_t st, size_t bytes) {

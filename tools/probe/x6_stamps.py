@@ -7,7 +7,13 @@ e4e + StyleGAN2 + VGG16) and prints, per kernel variant, the cycles per block sp
 the MFMA-only lower bound of the main loop (16 cycles per v_mfma_f32_16x16x32_bf16, two waves per
 SIMD) and the in-kernel clock (s_memtime / s_memrealtime × 100 MHz).
 
-Usage: python tools/probe/x6_stamps.py [--batch 128] [--pgd-steps 20]
+With --stagger 0 / 1 the 128-column tile runs its unstaggered / staggered K loop
+(MIA_X6_STAGGER); per variant a second line gives, for wave 0 and its SIMD partner wave 4, the mean
+cycles from a K-step's top (barrier release) to the start of its fragment reads, to its first
+MFMA, to its arrival at the step-end wait and to the release, and the partners' phase offset at
+the first MFMA as a fraction of the K-step.
+
+Usage: python tools/probe/x6_stamps.py [--batch 128] [--pgd-steps 20] [--stagger 0|1]
 """
 import argparse
 import ctypes
@@ -37,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--pgd-steps", type=int, default=20)
+    ap.add_argument("--stagger", type=int, default=-1, choices=[-1, 0, 1])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     T, S, B = torch.float32, 256, a.batch
@@ -51,7 +58,8 @@ def main():
     assert os.path.basename(_lib.LIB_PATH) == "libmiattack_stamps.so"
     fn = lib.mia_debug_x6_stamps
     fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]
-    buf = (ctypes.c_ulonglong * 64)()
+    buf = (ctypes.c_ulonglong * 96)()
+    _lib.set_tuning("MIA_X6_STAGGER", a.stagger)
     eng.run(x0, tgt, a.pgd_steps, 8 / 255, 2 / 255)
     torch.cuda.synchronize()
     assert fn(buf, 1) == 0
@@ -63,7 +71,7 @@ def main():
     assert fn(buf, 0) == 0
     print(f"attack {e0.elapsed_time(e1):.1f} ms")
     for v in range(4):
-        r = [buf[v * 16 + i] for i in range(16)]
+        r = [buf[v * 24 + i] for i in range(24)]
         nb = r[0]
         if not nb:
             continue
@@ -75,6 +83,12 @@ def main():
               f"loop {loop / tot:6.1%}  loop vs MFMA-only {ideal / loop:6.1%}  "
               f"clock {tot / rt * 0.1:5.2f} GHz  step-end wait+barrier: weights wave "
               f"{r[7] / loop:6.1%} halo wave {r[8] / loop:6.1%} of the loop")
+        if r[12]:
+            w0, w4 = [x / steps for x in r[9:13]], [x / steps for x in r[13:17]]
+            print(f"{'':11s} cycles from the K-step's top, wave 0 | wave 4: reads "
+                  f"{w0[0]:6.0f} | {w4[0]:6.0f}  first MFMA {w0[1]:6.0f} | {w4[1]:6.0f}  step-end "
+                  f"wait {w0[2]:6.0f} | {w4[2]:6.0f}  release {w0[3]:6.0f} | {w4[3]:6.0f}  "
+                  f"phase offset at the first MFMA {abs(w0[1] - w4[1]) / w0[3]:5.2f} of a K-step")
 
 
 if __name__ == "__main__":
