@@ -143,6 +143,9 @@ SIGNATURES = {
     "mia_mi_update": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float,
                               c_float, P, P]),
     "mia_ti_smooth_norms": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "mia_di_resize_pad": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "mia_di_resize_pad_bwd_norms": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            P, P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

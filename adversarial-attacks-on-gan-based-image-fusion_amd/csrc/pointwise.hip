@@ -1305,6 +1305,220 @@ __global__ __launch_bounds__(TPB) void ti_smooth_norms_kernel(
   block_slot_store<2>(s1, s2, part);
 }
 
+// ---- input diversity (torchattacks DIFGSM / TIFGSM input_diversity at a fixed image size) ------
+// y = D(x): every plane resized bilinearly (align_corners = False) to rnd × rnd and placed at
+// (top, left) of a zero S × S plane; gx = Dᵀ g with the per-image partial sums of |gx| and gx².
+// The source of output o along one axis is an exact rational: n = (2o+1)·S − rnd over d = 2·rnd,
+//   i0 = n / d,  i1 = min(i0 + 1, S − 1),  w1 = λ = float(n − i0·d) / float(d),
+//   w0 = float(d − (n − i0·d)) / float(d)
+// (unsigned 32-bit: n < 2·S² < 2^32 because S² < 2^31; each weight is one IEEE division of two
+// integers below 2^24, so w0 carries one rounding too instead of the two of 1 − λ). rnd ≤ S puts
+// every source coordinate in [0, S − 1], and i0 = S − 1 only with λ = 0.
+// A term whose weight is exactly 0 is left out and the sums start from −0, so rnd = S (every
+// λ = 0, every w0 = 1) returns its input bit for bit. No contraction: products and additions
+// round separately, forward  w0y·(w0x·a00 + w1x·a01) + w1y·(w0x·a10 + w1x·a11).
+//
+// Both kernels run one block per DI_TX × DI_TY tile of one plane on a (C·tiles, N) grid, a thread
+// on 4 adjacent columns of DI_TY / 4 rows (row = wave + 4·k, wave-uniform): the geometry depends
+// on (C, S) only. The per-column and per-row taps of the tile are worked out once per block into
+// LDS (one integer division pair per tap instead of per element); VEC moves the 4 columns as one
+// 16-byte vector (S % 4 == 0, aligned bases), the scalar form moves the same elements of the same
+// thread one by one: the same bits, sums included.
+constexpr int DI_TX = 256;  // tile columns: 64 lanes × 4
+constexpr int DI_TY = 32;   // tile rows: 4 waves × 8
+
+// forward tap of output o ∈ [0, rnd): source index i0 and the weights of i0 and i0 + 1
+__device__ __forceinline__ void di_src(uint32_t o, uint32_t S, uint32_t rnd, int& i0, float& w0,
+                                       float& w1) {
+#pragma clang fp contract(off)
+  const uint32_t d = 2u * rnd;
+  const uint32_t n = (2u * o + 1u) * S - rnd;
+  const uint32_t q = n / d, r = n - q * d;
+  i0 = (int)q;
+  w0 = (float)(d - r) / (float)d;
+  w1 = (float)r / (float)d;
+}
+
+// adjoint tap of input i: the one output o with i0(o) == i (source coordinates are ≥ 1 apart, so
+// there is at most one), or o = −1. i0(o) = i ⟺ (2i+1)·rnd ≤ (2o+1)·S < (2i+3)·rnd: the
+// candidate is the smallest o that meets the left inequality, kept if the forward rule maps it to
+// i. Input i then receives w0(o)·g[o] from this tap and w1(o')·g[o'] from the tap of i − 1.
+__device__ __forceinline__ void di_adj(int i, int S, int rnd, int& o, float& w0, float& w1) {
+  o = -1;
+  w0 = w1 = 0.f;
+  if (i < 0 || i >= S) return;
+  const uint32_t a = (2u * (uint32_t)i + 1u) * (uint32_t)rnd;  // < 2·S²
+  const uint32_t c = a <= (uint32_t)S ? 0u : (a + (uint32_t)S - 1u) / (2u * (uint32_t)S);
+  if (c >= (uint32_t)rnd) return;
+  int i0;
+  float f0, f1;
+  di_src(c, S, rnd, i0, f0, f1);
+  if (i0 != i) return;
+  o = (int)c;
+  w0 = f0;
+  w1 = f1;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void di_resize_pad_kernel(const float* __restrict__ x,
+                                                            float* __restrict__ y, int C, int S,
+                                                            int rnd, int top, int left,
+                                                            int tiles_x, int tiles_y) {
+#pragma clang fp contract(off)
+  __shared__ int si[DI_TX + DI_TY];  // columns of the tile, then its rows; −1 outside the window
+  __shared__ float sw0[DI_TX + DI_TY], sw1[DI_TX + DI_TY];
+  const int t = threadIdx.x, n = blockIdx.y;
+  const int tiles = tiles_x * tiles_y;
+  const int c = blockIdx.x / tiles, tile = blockIdx.x - c * tiles;
+  const int ry0 = (tile / tiles_x) * DI_TY, cx0 = (tile % tiles_x) * DI_TX;
+  for (int j = t; j < DI_TX + DI_TY; j += TPB) {
+    const int o = j < DI_TX ? cx0 + j - left : ry0 + (j - DI_TX) - top;
+    int i0 = -1;
+    float w0 = 0.f, w1 = 0.f;
+    if (o >= 0 && o < rnd) di_src(o, S, rnd, i0, w0, w1);
+    si[j] = i0;
+    sw0[j] = w0;
+    sw1[j] = w1;
+  }
+  __syncthreads();
+  const int lane = t & 63, wv = t >> 6;
+  const int x0 = cx0 + 4 * lane;
+  if (x0 >= S) return;
+  const int64_t pbase = ((int64_t)n * C + c) * ((int64_t)S * S);
+  const float* __restrict__ xp = x + pbase;
+  float* __restrict__ yp = y + pbase;
+  int ix[4];
+  float wx0[4], wx1[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    ix[e] = si[4 * lane + e];
+    wx0[e] = sw0[4 * lane + e];
+    wx1[e] = sw1[4 * lane + e];
+  }
+  for (int k = 0; k < DI_TY / 4; ++k) {
+    const int yy = ry0 + wv + 4 * k;
+    if (yy >= S) break;
+    const int jy = DI_TX + wv + 4 * k;
+    const int iy = si[jy];
+    const float wy0 = sw0[jy], wy1 = sw1[jy];
+    float o4[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v = 0.f;
+      if (iy >= 0 && ix[e] >= 0) {
+        const bool hx = wx1[e] > 0.f, hy = wy1 > 0.f;
+        const float* __restrict__ r0 = xp + (int64_t)iy * S;
+        const float* __restrict__ r1 = xp + (int64_t)min(iy + 1, S - 1) * S;
+        const int i0 = ix[e], i1 = min(ix[e] + 1, S - 1);
+        const float t0 = wx0[e] * r0[i0];
+        const float u0 = hx ? wx1[e] * r0[i1] : -0.f;
+        const float s0 = t0 + u0;
+        float s1 = -0.f;
+        if (hy) {
+          const float t1 = wx0[e] * r1[i0];
+          const float u1 = hx ? wx1[e] * r1[i1] : -0.f;
+          s1 = wy1 * (t1 + u1);
+        }
+        v = wy0 * s0 + s1;
+      }
+      o4[e] = v;
+    }
+    float* __restrict__ dst = yp + (int64_t)yy * S + x0;
+    if (VEC) {
+      stv<4>(dst, o4);  // S % 4 == 0: the vector is whole
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (x0 + e < S) dst[e] = o4[e];
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void di_resize_pad_bwd_norms_kernel(
+    const float* __restrict__ g, float* __restrict__ gx, float* __restrict__ part, int C, int S,
+    int rnd, int top, int left, int tiles_x, int tiles_y, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  // adjoint taps of columns cx0 − 1 … cx0 + DI_TX − 1, then of rows ry0 − 1 … ry0 + DI_TY − 1
+  constexpr int NT = DI_TX + 1 + DI_TY + 1;
+  __shared__ int so[NT];
+  __shared__ float sw0[NT], sw1[NT];
+  const int t = threadIdx.x, n = blockIdx.y;
+  const int tiles = tiles_x * tiles_y;
+  const int c = blockIdx.x / tiles, tile = blockIdx.x - c * tiles;
+  const int ry0 = (tile / tiles_x) * DI_TY, cx0 = (tile % tiles_x) * DI_TX;
+  for (int j = t; j < NT; j += TPB) {
+    const int i = j <= DI_TX ? cx0 - 1 + j : ry0 - 1 + (j - DI_TX - 1);
+    di_adj(i, S, rnd, so[j], sw0[j], sw1[j]);
+  }
+  __syncthreads();
+  const int lane = t & 63, wv = t >> 6;
+  const int x0 = cx0 + 4 * lane;
+  const int64_t pbase = ((int64_t)n * C + c) * ((int64_t)S * S);
+  const float* __restrict__ gp = g + pbase + (int64_t)top * S + left;  // the window's origin
+  float* __restrict__ op = gx + pbase;
+  float a1[4], a2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a1[e] = a2[e] = 0.f;
+  bool bad = false;
+  if (x0 < S) {
+    // column x0 − 1 + k: its output ox[k]; it gives column x0 − 1 + k weight wa[k] and column
+    // x0 + k weight wb[k]
+    int ox[5];
+    float wa[5], wb[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      ox[k] = so[4 * lane + k];
+      wa[k] = sw0[4 * lane + k];
+      wb[k] = sw1[4 * lane + k];
+    }
+    for (int k = 0; k < DI_TY / 4; ++k) {
+      const int yy = ry0 + wv + 4 * k;
+      if (yy >= S) break;
+      const int jy = DI_TX + 1 + wv + 4 * k;  // the tap of row yy − 1; jy + 1: of row yy
+      const int oyB = so[jy], oyA = so[jy + 1];
+      const float wyB = sw1[jy], wyA = sw0[jy + 1];
+      const bool hB = oyB >= 0 && wyB > 0.f, hA = oyA >= 0;
+      float vB[5], vA[5];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        vB[j] = hB && ox[j] >= 0 ? gp[(int64_t)oyB * S + ox[j]] : 0.f;
+        vA[j] = hA && ox[j] >= 0 ? gp[(int64_t)oyA * S + ox[j]] : 0.f;
+      }
+      float o4[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        // oy ascending (B before A), then ox ascending (the tap of column − 1 first)
+        const bool xB = ox[e] >= 0 && wb[e] > 0.f, xA = ox[e + 1] >= 0;
+        const float pB0 = xB ? wb[e] * vB[e] : -0.f;
+        const float pB1 = xA ? wa[e + 1] * vB[e + 1] : -0.f;
+        const float pA0 = xB ? wb[e] * vA[e] : -0.f;
+        const float pA1 = xA ? wa[e + 1] * vA[e + 1] : -0.f;
+        const float sB = pB0 + pB1, sA = pA0 + pA1;
+        const float qB = hB ? wyB * sB : -0.f;
+        const float qA = hA ? wyA * sA : -0.f;
+        const float v = (xB || xA) && (hB || hA) ? qB + qA : 0.f;
+        o4[e] = v;
+        if (VEC || x0 + e < S) {
+          bad |= !__builtin_isfinite(v);
+          a1[e] += fabsf(v);
+          a2[e] = fmaf(v, v, a2[e]);
+        }
+      }
+      float* __restrict__ dst = op + (int64_t)yy * S + x0;
+      if (VEC) {
+        stv<4>(dst, o4);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (x0 + e < S) dst[e] = o4[e];
+      }
+    }
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+  block_slot_store<2>(lane_sum<4>(a1), lane_sum<4>(a2), part);
+}
+
 // ---- C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1, 1]:
 // adv = tanh(w) (= 2·½(tanh w + 1) − 1), w0 = atanh(x) with x clamped to ±(1 − 2⁻²⁰) so that
 // saturated pixels stay finite.
@@ -1920,6 +2134,57 @@ extern "C" int mia_ti_smooth_norms(const float* g, float* gs, const float* taps,
     hipLaunchKernelGGL(ti_smooth_norms_kernel<1>, grid, dim3(TPB), lds, st, g, gs, taps, K,
                        r.part, C, H, W, tiles_x, tiles_y, nonfinite);
   rc = check_launch("ti_smooth_norms_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+// the checks shared by the two input-diversity entry points; a and b: N·C·S² floats each
+#define MIA_CHECK_DI(a, b, N, C, S, rnd, top, left)                                           \
+  MIA_CHECK_ARG((a) && (b), "null buffer");                                                   \
+  MIA_CHECK_ARG((C) > 0 && (S) > 0, "C and S must be > 0");                                   \
+  MIA_CHECK_ARG((int64_t)(S) * (S) < (1LL << 31), "C·S² must be below 2^31");                 \
+  MIA_CHECK_IMAGES(N, (int64_t)(C) * (S) * (S));                                              \
+  MIA_CHECK_ARG((rnd) >= 1 && (rnd) <= (S), "rnd must be in 1 … S");                          \
+  MIA_CHECK_ARG((top) >= 0 && (top) <= (S) - (rnd) && (left) >= 0 && (left) <= (S) - (rnd),   \
+                "need top, left >= 0, top + rnd <= S and left + rnd <= S");                   \
+  MIA_CHECK_ARG(!di_overlap(a, b, (int64_t)(N) * (C) * (S) * (S)),                            \
+                "the input and the output must be distinct buffers")
+
+static inline bool di_overlap(const float* a, const float* b, int64_t len) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = (uintptr_t)len * sizeof(float);
+  return pa < pb ? pb - pa < bytes : pa - pb < bytes;
+}
+
+extern "C" int mia_di_resize_pad(const float* x, float* y, int N, int C, int S, int rnd, int top,
+                                 int left, void* stream) {
+  MIA_CHECK_DI(x, y, N, C, S, rnd, top, left);
+  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(y);
+  const int tiles_x = (S + DI_TX - 1) / DI_TX, tiles_y = (S + DI_TY - 1) / DI_TY;
+  const dim3 grid(C * tiles_x * tiles_y, N);  // ≤ plane < 2^31 blocks per row
+  if (vec)
+    MIA_LAUNCH(di_resize_pad_kernel<true>, grid, dim3(TPB), 0, x, y, C, S, rnd, top, left,
+               tiles_x, tiles_y);
+  MIA_LAUNCH(di_resize_pad_kernel<false>, grid, dim3(TPB), 0, x, y, C, S, rnd, top, left, tiles_x,
+             tiles_y);
+}
+
+extern "C" int mia_di_resize_pad_bwd_norms(const float* g, float* gx, float* l1, float* l2sq,
+                                           int N, int C, int S, int rnd, int top, int left,
+                                           int* nonfinite, void* stream) {
+  MIA_CHECK_DI(g, gx, N, C, S, rnd, top, left);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = S % 4 == 0 && aligned16(g) && aligned16(gx);
+  const int tiles_x = (S + DI_TX - 1) / DI_TX, tiles_y = (S + DI_TY - 1) / DI_TY;
+  const dim3 grid(C * tiles_x * tiles_y, N);
+  RedQ r;
+  int rc = red_begin(r, l1, l2sq, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  if (vec)
+    hipLaunchKernelGGL(di_resize_pad_bwd_norms_kernel<true>, grid, dim3(TPB), 0, st, g, gx,
+                       r.part, C, S, rnd, top, left, tiles_x, tiles_y, nonfinite);
+  else
+    hipLaunchKernelGGL(di_resize_pad_bwd_norms_kernel<false>, grid, dim3(TPB), 0, st, g, gx,
+                       r.part, C, S, rnd, top, left, tiles_x, tiles_y, nonfinite);
+  rc = check_launch("di_resize_pad_bwd_norms_kernel");
   return rc != MIA_OK ? rc : red_finish(r, st);
 }
 

@@ -54,7 +54,11 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       FloatingPointError on EVERY rank (an empty-shard rank included) before the all-gather, so
       no rank is left blocked in the collective.
     * Every other keyword (``norm``, ``momentum``, ``ti_kernel``, ``ti_nsig``, …) is forwarded to
-      ``pgd.attack`` unchanged; the TI smoothing acts per image plane, so it is shard-local."""
+      ``pgd.attack`` unchanged; the TI smoothing acts per image plane, so it is shard-local.
+    * Input diversity (``di_prob``, ``di_resize_rate``, ``di_schedule``) is shard-local too: the
+      draws are a host schedule that every rank computes from ``seed`` alone
+      (``pgd.make_di_schedule``; one draw per step serves the whole batch), and the transform
+      acts per image plane, so the output does not depend on the world size."""
     from . import pgd
     group = group if group is not None else dist.group.WORLD
     world = dist.get_world_size(group)

@@ -2,6 +2,7 @@
 out. Every wrapper validates shapes/dtypes/contiguity on the host before a kernel is launched, so a
 malformed call raises here instead of faulting on the GPU."""
 import ctypes
+import numbers
 
 import torch
 
@@ -635,6 +636,47 @@ def ti_smooth_norms(g, taps, gs, l1, l2sq, nonfinite=None):
     call("mia_ti_smooth_norms", ptr(g), ptr(gs), ptr(taps), K, ptr(l1), ptr(l2sq), N, C, H, W,
          ptr(nonfinite), stream())
     return gs
+
+
+def _di_args(x, y, rnd, top, left, xname, yname):
+    """Shared checks of the input-diversity pair: distinct fp32 (N,C,S,S) tensors and a window
+    rnd × rnd at (top, left) inside S × S. Returns (N, C, S, rnd, top, left) as ints."""
+    if x is None or x.dim() != 4 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError(f"{xname} must be a non-empty fp32 (N,C,S,S) tensor")
+    N, C, S, S2 = x.shape
+    if S != S2:
+        raise ValueError(f"{xname} must have square planes (N,C,S,S)")
+    _need(y, x.shape, torch.float32, yname)
+    if y.data_ptr() == x.data_ptr():
+        raise ValueError(f"{xname} and {yname} must be distinct buffers")
+    for v in (rnd, top, left):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("rnd, top and left must be integers")
+    rnd, top, left = int(rnd), int(top), int(left)
+    if not (1 <= rnd <= S and 0 <= top <= S - rnd and 0 <= left <= S - rnd):
+        raise ValueError("need 1 <= rnd <= S, top, left >= 0, top + rnd <= S and left + rnd <= S")
+    return N, C, S, rnd, top, left
+
+
+def di_resize_pad(x, y, rnd, top, left):
+    """y ← D(x): every plane of x resized bilinearly (align_corners=False) to rnd × rnd and placed
+    at (top, left) of a zero S × S plane — torchattacks input_diversity at a fixed image size
+    (mia_di_resize_pad). x, y: distinct fp32 (N,C,S,S)."""
+    N, C, S, rnd, top, left = _di_args(x, y, rnd, top, left, "x", "y")
+    call("mia_di_resize_pad", ptr(x), ptr(y), N, C, S, rnd, top, left, stream())
+    return y
+
+
+def di_resize_pad_bwd_norms(g, gx, l1, l2sq, rnd, top, left, nonfinite=None):
+    """gx ← Dᵀ g, the adjoint of di_resize_pad, with l1[n] += Σ|gx_n| and l2sq[n] += Σ gx_n²
+    (either may be None) (mia_di_resize_pad_bwd_norms). g, gx: distinct fp32 (N,C,S,S)."""
+    N, C, S, rnd, top, left = _di_args(g, gx, rnd, top, left, "g", "gx")
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    call("mia_di_resize_pad_bwd_norms", ptr(g), ptr(gx), ptr(l1), ptr(l2sq), N, C, S, rnd, top,
+         left, ptr(nonfinite), stream())
+    return gx
 
 
 def cw_init(x, w):

@@ -17,6 +17,8 @@ together (per-image MSE means; a batch's gradient equals the reference's per-ima
 The loss is never materialised on the device unless ``return_info`` asks for it: PGD needs only
 sign(∇L), so there is no per-step host synchronisation.
 """
+import numbers
+
 import numpy as np
 import torch
 
@@ -434,6 +436,28 @@ class AttackEngine:
         gs = self.ws.get("g.ti", x.shape, torch.float32)
         return ops.ti_smooth_norms(g, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
 
+    def _di_grad_norms(self, x, di, taps, l1, l2sq):
+        """The input-diversity gradient g = Dᵀ ∇L(D x) for di = (rnd, top, left) (host integers):
+        xd = D(x) (ops.di_resize_pad, buffer di.x), the objective's gradient AT xd (unscaled, as
+        _grad_norms; the 10·MSE(x0, ·) term and both networks read xd), then its adjoint
+        (ops.di_resize_pad_bwd_norms, buffer g.di). Without taps the per-image Σ|g| / Σg² are
+        taken there; with taps the TI smoothing follows and takes them (buffer g.ti). Returns the
+        gradient the update kernel reads."""
+        rnd, top, left = di
+        ws, f32 = self.ws, torch.float32
+        xd = ops.di_resize_pad(x, ws.get("di.x", x.shape, f32), rnd, top, left)
+        g = ws.get("g.full", x.shape, f32)
+        g_xv, g_enc = self.gradient(xd)
+        ops.grad_assemble(xd, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
+                          1.0 / self.loss_scale, nonfinite=self.nonfinite)
+        gx = ws.get("g.di", x.shape, f32)
+        if taps is None:
+            return ops.di_resize_pad_bwd_norms(g, gx, l1, l2sq, rnd, top, left,
+                                               nonfinite=self.nonfinite)
+        ops.di_resize_pad_bwd_norms(g, gx, None, None, rnd, top, left, nonfinite=self.nonfinite)
+        gs = ws.get("g.ti", x.shape, f32)
+        return ops.ti_smooth_norms(gx, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
+
     def ti_device_taps(self, taps):
         """The 1-D taps (ti_gaussian_taps) rounded once to fp32, on the engine's device."""
         t = torch.as_tensor(taps, dtype=torch.float64).reshape(-1)
@@ -441,11 +465,16 @@ class AttackEngine:
             raise ValueError("ti_taps must hold an odd number of values, 1 … 63")
         return t.to(torch.float32).to(self.G.device).contiguous()
 
-    def step_l2(self, x, a, e, ti_taps=None):
+    def step_l2(self, x, a, e, ti_taps=None, di=None):
         """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units.
-        ``ti_taps`` (fp32 device taps, ti_device_taps): the step follows the smoothed gradient."""
+        ``ti_taps`` (fp32 device taps, ti_device_taps): the step follows the smoothed gradient.
+        ``di`` (a make_di_schedule row (rnd, top, left, apply) of host integers): with apply = 1
+        the gradient is Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or None is the plain step."""
         sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
-        if ti_taps is None:
+        di = _di_row(di)
+        if di is not None:
+            g = self._di_grad_norms(x, di, ti_taps, None, sums[0])
+        elif ti_taps is None:
             g = self.ws.get("g.full", x.shape, torch.float32)
             self._grad_norms(x, g, None, sums[0])  # sums: Σg², Σ(adv − x0)² per image
         else:
@@ -454,12 +483,17 @@ class AttackEngine:
         ops.l2_project(x, self.x0, sums[1], _f32(e))
         return x
 
-    def step_mi(self, x, m, momentum, a, e, ti_taps=None):
+    def step_mi(self, x, m, momentum, a, e, ti_taps=None, di=None):
         """One momentum iterative FGSM step on x and the momentum buffer m, both in place.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the TI-FGSM step, on the smoothed
-        gradient and its mean."""
+        gradient and its mean. ``di`` (a make_di_schedule row (rnd, top, left, apply) of host
+        integers): with apply = 1 the DI-FGSM step, on Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or
+        None is the step without input diversity."""
         l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
-        if ti_taps is None:
+        di = _di_row(di)
+        if di is not None:
+            g = self._di_grad_norms(x, di, ti_taps, l1, None)
+        elif ti_taps is None:
             g = self.ws.get("g.full", x.shape, torch.float32)
             self._grad_norms(x, g, l1, None)
         else:
@@ -469,44 +503,54 @@ class AttackEngine:
         return x
 
     def run_l2(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None,
-               ti_taps=None):
+               ti_taps=None, di=None):
         """L2-ball PGD (torchattacks PGDL2.forward) descending L: per image
         x ← x + a·(−g)/(‖g‖₂ + 1e-10); d = x − x0; x ← clamp(x0 + d·min(e/‖d‖₂, 1), −1, 1), with
         e = 2·eps, a = 2·alpha. ``start_noise``: make_start_noise(shape, seed, "l2"). The norms
         stay on the device (ordered reductions): no per-step host synchronisation.
-        ``ti_taps`` (1-D taps, ti_gaussian_taps): g is replaced by (taps ⊗ taps) ⋆ g."""
+        ``ti_taps`` (1-D taps, ti_gaussian_taps): g is replaced by (taps ⊗ taps) ⋆ g.
+        ``di`` (a (steps, 4) schedule, make_di_schedule): step k with apply = 1 follows
+        Dₖᵀ ∇L(Dₖ x) (smoothed after the adjoint when ti_taps is given). The schedule is host
+        data fixed before the loop, so an fp16 loss-scale re-run replays the same draws."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
+        rows = _di_rows(di, steps, self.size)
         return self._with_rescale(
-            lambda: self._run_l2(x0, t, steps, eps, alpha, random_start, start_noise, taps),
-            group)
+            lambda: self._run_l2(x0, t, steps, eps, alpha, random_start, start_noise, taps,
+                                 rows), group)
 
-    def _run_l2(self, x0, t, steps, eps, alpha, random_start, start_noise, ti_taps=None):
+    def _run_l2(self, x0, t, steps, eps, alpha, random_start, start_noise, ti_taps=None,
+                di=None):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
-        for _ in range(steps):
-            self.step_l2(x, a, e, ti_taps)
+        for k in range(steps):
+            self.step_l2(x, a, e, ti_taps, None if di is None else di[k])
         return x.clone()
 
     def run_mi(self, x0, t, steps, eps, alpha, momentum=1.0, random_start=False, start_noise=None,
-               group=None, ti_taps=None):
+               group=None, ti_taps=None, di=None):
         """Momentum iterative FGSM (torchattacks MIFGSM.forward) descending L: per image
         ĝ = (−g)/mean|g|; m ← ĝ + μ·m (m = 0 at the start);
         x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1), with e = 2·eps, a = 2·alpha.
         An image whose gradient is all zero (0/0) is reported like an overflow, never left frozen
         silently. ``ti_taps`` (1-D taps, ti_gaussian_taps): torchattacks TIFGSM without input
-        diversity, g replaced by (taps ⊗ taps) ⋆ g before the normalisation."""
+        diversity, g replaced by (taps ⊗ taps) ⋆ g before the normalisation.
+        ``di`` (a (steps, 4) schedule, make_di_schedule): torchattacks DIFGSM (TIFGSM with
+        ti_taps) — step k with apply = 1 uses g = Dₖᵀ ∇L(Dₖ x), Dₖ the step's resize-and-pad
+        (smoothed after the adjoint when ti_taps is given). The schedule is host data fixed before
+        the loop, so an fp16 loss-scale re-run replays the same draws."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
+        rows = _di_rows(di, steps, self.size)
         return self._with_rescale(
             lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                                 taps), group)
+                                 taps, rows), group)
 
     def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                ti_taps=None):
+                ti_taps=None, di=None):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
         m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
-        for _ in range(steps):
-            self.step_mi(x, m, momentum, a, e, ti_taps)
+        for k in range(steps):
+            self.step_mi(x, m, momentum, a, e, ti_taps, None if di is None else di[k])
         return x.clone()
 
 
@@ -540,6 +584,107 @@ def ti_gaussian_taps(kernlen=15, nsig=3.0):
     return torch.from_numpy(k / k.sum())
 
 
+# make_di_schedule's generator is seeded with (seed + DI_SEED_OFFSET) mod 2^63 ("DI-FGSM" in
+# ASCII): a stream of its own, never make_start_noise's manual_seed(seed) replayed.
+DI_SEED_OFFSET = 0x44492D4647534D
+
+
+def _check_di_rate(size, resize_rate):
+    """lo = int(size·resize_rate), the smallest resized edge; it must lie in 1 … size − 1."""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 2:
+        raise ValueError("the image size must be an integer >= 2")
+    if isinstance(resize_rate, bool) or not isinstance(resize_rate, numbers.Real):
+        raise ValueError("di_resize_rate must be a number")
+    rate = float(resize_rate)
+    if not np.isfinite(rate):
+        raise ValueError("di_resize_rate must be finite")
+    lo = int(size * rate)
+    if not 1 <= lo <= size - 1:
+        raise ValueError(
+            f"di_resize_rate must give 1 <= int(size * rate) <= size - 1 (got {lo} at size "
+            f"{size}): the networks are fixed-size, so rates >= 1 (torchattacks' enlarging "
+            "form) are not supported")
+    return lo
+
+
+def _check_di_prob(prob):
+    if (isinstance(prob, bool) or not isinstance(prob, numbers.Real)
+            or not 0.0 <= float(prob) <= 1.0):  # NaN fails the comparison
+        raise ValueError("di_prob must be a number in [0, 1]")
+    return float(prob)
+
+
+def make_di_schedule(steps, size, resize_rate=0.9, diversity_prob=0.5, seed=0):
+    """The input-diversity draws of a whole attack: a host int64 (steps, 4) tensor of rows
+    (rnd, top, left, apply), torchattacks ``input_diversity`` at a fixed image size ``size``:
+
+        lo = int(size·resize_rate);  rnd = randint(lo, size)          lo <= rnd <= size − 1
+        top = randint(0, size − rnd);  left = randint(0, size − rnd)  top + rnd <= size − 1
+        apply = rand() < diversity_prob
+
+    One row per step serves the whole batch (as torchattacks). The draws match torchattacks in
+    distribution and order, not in values: they come from a generator of their own, seeded with
+    (seed + DI_SEED_OFFSET) mod 2^63, and are taken step by step in the fixed order rnd, top,
+    left, apply — one scalar draw each, all four at every step whatever ``apply`` turns out to be
+    — so a shorter schedule of the same seed is a prefix of a longer one. Computed before the
+    loop: a loss-scale re-run replays it, every rank of ``attack_distributed`` computes the same
+    one, and an image's result does not depend on the batch or world size."""
+    if isinstance(steps, bool) or int(steps) != steps or steps < 0:
+        raise ValueError("need integer steps >= 0")
+    lo = _check_di_rate(size, resize_rate)
+    p = _check_di_prob(diversity_prob)
+    size = int(size)
+    g = torch.Generator().manual_seed((int(seed) + DI_SEED_OFFSET) % (1 << 63))
+    rows = []
+    for _ in range(int(steps)):
+        rnd = int(torch.randint(lo, size, (1,), generator=g))
+        top = int(torch.randint(0, size - rnd, (1,), generator=g))
+        left = int(torch.randint(0, size - rnd, (1,), generator=g))
+        u = float(torch.rand((1,), dtype=torch.float64, generator=g))
+        rows.append((rnd, top, left, int(u < p)))
+    return torch.tensor(rows, dtype=torch.int64).reshape(int(steps), 4)
+
+
+def check_di_schedule(schedule, steps, size):
+    """An explicit schedule as a host int64 (steps, 4) tensor: rows (rnd, top, left, apply) with
+    1 <= rnd <= size, top, left >= 0, top + rnd <= size, left + rnd <= size (the kernels'
+    constraints; rnd = size is the identity) and apply in {0, 1}."""
+    try:
+        s = torch.as_tensor(schedule)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("di_schedule must be an integer (steps, 4) tensor") from None
+    if s.is_floating_point() or s.is_complex() or s.dtype == torch.bool:
+        raise ValueError("di_schedule must hold integers")
+    if s.dim() != 2 or tuple(s.shape) != (int(steps), 4):
+        raise ValueError(f"di_schedule must have shape (steps, 4) = ({int(steps)}, 4)")
+    s = s.detach().to("cpu", torch.int64)
+    rnd, top, left, ap = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+    ok = ((rnd >= 1) & (rnd <= size) & (top >= 0) & (left >= 0) & (top <= size - rnd)
+          & (left <= size - rnd) & ((ap == 0) | (ap == 1)))
+    if not bool(ok.all()):
+        k = int((~ok).nonzero()[0])
+        raise ValueError(f"di_schedule row {k} = {s[k].tolist()}: need 1 <= rnd <= {size}, "
+                         "top, left >= 0, top + rnd <= size, left + rnd <= size, apply in {0, 1}")
+    return s
+
+
+def _di_rows(schedule, steps, size):
+    """run_*'s ``di``: None, or the checked schedule as a list of host-integer rows."""
+    if schedule is None:
+        return None
+    return check_di_schedule(schedule, steps, size).tolist()
+
+
+def _di_row(di):
+    """step_*'s ``di``: (rnd, top, left) of a row with apply = 1, None for apply = 0 / None."""
+    if di is None:
+        return None
+    rnd, top, left, ap = (int(v) for v in di)
+    if ap not in (0, 1):
+        raise ValueError("di: apply must be 0 or 1")
+    return (rnd, top, left) if ap else None
+
+
 def make_start_noise(shape, seed, norm="linf"):
     """The random-start draw of the FULL batch shape (scaled by e in the kernel, x = clamp(x0 +
     e·u)); ``attack_distributed`` slices it per shard so every world size sees the same noise.
@@ -562,7 +707,8 @@ def make_start_noise(shape, seed, norm="linf"):
 
 def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_start=False,
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
-           lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0):
+           lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
+           di_prob=None, di_resize_rate=0.9, di_schedule=None):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -604,6 +750,21 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             norm='l2' takes the PGDL2 step above along W ⋆ ∇L and its L2 norm
             (AttackEngine.run_mi / run_l2 with ti_taps).
     ti_nsig  the Gaussian's half-width in standard deviations (torchattacks' nsig, 3).
+    di_prob  None (default): no input diversity. p in [0, 1], with norm='linf' or 'l2': the
+            diverse-input attack (torchattacks DIFGSM; TIFGSM together with ti_kernel, whose own
+            default is diversity_prob = 0.5). Per step, with probability p, one random
+            resize-and-pad D serves the whole batch (fused HIP kernels, both directions):
+                      D(x) = zero_pad(bilinear(x, (rnd, rnd), align_corners=False), top, left)
+            with int(S·di_resize_rate) <= rnd <= S − 1 and the pad offsets drawn as torchattacks
+            does. The whole objective is evaluated at D(x) (the targets stay those of x0 and t)
+            and the step follows g = Dᵀ ∇L(D x); then the smoothing, if any, and the update of
+            ``norm`` run as without it: the MIFGSM rule for 'linf' (momentum=None means μ = 0,
+            torchattacks DIFGSM's / TIFGSM's default decay), PGDL2 for 'l2'. The draws come from
+            ``make_di_schedule(steps, S, di_resize_rate, di_prob, seed)`` before the loop.
+    di_resize_rate  torchattacks' resize_rate, below 1 (default 0.9): the smallest resized edge is
+            int(S·rate). Rates >= 1 would change the networks' input size and are rejected.
+    di_schedule  an explicit host (steps, 4) integer schedule of rows (rnd, top, left, apply)
+            instead of the seeded draws (``check_di_schedule``; rnd = S is the identity).
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
     Returns the adversarial images on the input's device (fp32), and a dict if return_info.
@@ -620,6 +781,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if norm not in ("linf", "l2"):
             raise ValueError("ti_kernel (TI-FGSM) is implemented for norm='linf' and 'l2' only")
         ti_taps = ti_gaussian_taps(ti_kernel, ti_nsig)
+    use_di = di_prob is not None or di_schedule is not None
+    if use_di and norm not in ("linf", "l2"):
+        raise ValueError("input diversity (DI-FGSM) is implemented for norm='linf' and 'l2' only")
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
@@ -635,6 +799,14 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         raise ValueError("target batch must be 1 or match imgs")
     if steps < 0 or int(steps) != steps:
         raise ValueError("need integer steps >= 0")
+    di = None
+    if use_di:
+        if di_prob is not None:
+            _check_di_prob(di_prob)
+        if di_schedule is not None:
+            di = check_di_schedule(di_schedule, steps, size)
+        else:
+            di = make_di_schedule(int(steps), size, di_resize_rate, di_prob, seed)
     if norm in ("linf", "l2") and not (eps is not None and eps > 0 and alpha > 0):
         raise ValueError("PGD needs eps > 0 and alpha > 0")
     if norm in ("adam", "l2_cw") and not lr > 0:
@@ -661,16 +833,16 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf" and (momentum is not None or ti_taps is not None):
+    if norm == "linf" and (momentum is not None or ti_taps is not None or di is not None):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
                          float(momentum) if momentum is not None else 0.0, random_start, noise,
-                         group=group, ti_taps=ti_taps)
+                         group=group, ti_taps=ti_taps, di=di)
     elif norm == "linf":
         adv = eng.run(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
                       group=group)
     elif norm == "l2":
         adv = eng.run_l2(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
-                         group=group, ti_taps=ti_taps)
+                         group=group, ti_taps=ti_taps, di=di)
     elif norm == "adam":
         adv = eng.run_adam(x0, t, int(steps), lr=float(lr), group=group)
     else:
@@ -679,7 +851,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     if return_info:
         info = dict(loss=eng.loss(adv.to(dev)), steps=int(steps), eps=eps, alpha=alpha, norm=norm,
                     momentum=momentum, ti_kernel=ti_kernel, dtype=str(eng.dtype),
-                    loss_scale=eng.loss_scale, rescales=eng.rescales)
+                    loss_scale=eng.loss_scale, rescales=eng.rescales, di_prob=di_prob,
+                    di_resize_rate=di_resize_rate if di_prob is not None else None,
+                    di_applied=int(di[:, 3].sum()) if di is not None else 0)
         return adv, info
     return adv
 

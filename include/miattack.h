@@ -441,6 +441,35 @@ int mia_mi_update(float* x, const float* x0, const float* g, const float* l1, fl
  * mia_mi_update / mia_l2_step from device memory. */
 int mia_ti_smooth_norms(const float* g, float* gs, const float* taps, int K, float* l1,
                         float* l2sq, int N, int C, int H, int W, int* nonfinite, void* stream);
+/* Input diversity (torchattacks DIFGSM / TIFGSM input_diversity at a fixed image size S): per
+ * plane,  y = D(x) = zero_pad(bilinear(x, (rnd, rnd), align_corners = False), top, left),  S × S.
+ * x, y: fp32 (N,C,S,S) in distinct buffers; 1 ≤ rnd ≤ S, top, left ≥ 0, top + rnd ≤ S,
+ * left + rnd ≤ S, N in 1 … 65535, C·S² < 2^31 (anything else: MIA_EINVAL before any launch).
+ * Source coordinates are exact integers: output o of one axis reads
+ *   n = (2o+1)·S − rnd, d = 2·rnd:  i0 = n / d,  i1 = min(i0 + 1, S − 1),
+ *   w1 = float(n − i0·d) / float(d),  w0 = float(d − (n − i0·d)) / float(d)
+ * (one IEEE division each; PyTorch's align_corners = False rule without a rounded coordinate),
+ *   y[oy, ox] = w0y·(w0x·x[i0y,i0x] + w1x·x[i0y,i1x]) + w1y·(w0x·x[i1y,i0x] + w1x·x[i1y,i1x])
+ * one fp32 rounding per operation, no contraction; a term whose weight is exactly 0 is left
+ * out, so rnd = S (top = left = 0) returns x bit for bit. An element's value depends on its plane
+ * and position only. S % 4 == 0 with 16-byte aligned x / y stores 16-byte vectors, anything else
+ * scalars (the same bits). */
+int mia_di_resize_pad(const float* x, float* y, int N, int C, int S, int rnd, int top, int left,
+                      void* stream);
+/* The adjoint of mia_di_resize_pad with the per-image norms of the result, in one pass:
+ *   gx = Dᵀ g,  l1[n] += Σ|gx_n|,  l2sq[n] += Σ gx_n²   (fp32 [N], either may be NULL; ordered
+ *   reductions as in mia_grad_assemble_norms: one partial per 256 × 32 tile of each plane, a
+ *   geometry that depends on (C, S) only).
+ * g, gx: fp32 (N,C,S,S), distinct buffers; the arguments and weights of mia_di_resize_pad. A
+ * gather: with rnd < S consecutive source coordinates are more than 1 apart, so an input index
+ * receives at most 2 outputs per axis, found by the same integer arithmetic, and every gx
+ * element is the sum of at most 4 terms wy·(wx·g + wx'·g') + wy'·(…) added in a fixed order (oy
+ * ascending, then ox), written by exactly one thread; elements outside the window's support
+ * are 0. Reruns are bit-identical, an image's gx and sums do not depend on the other images, the
+ * vector and scalar forms (as above) give the same bits, sums included, and rnd = S returns g
+ * bit for bit. nonfinite (NULL or int[N]) is set for an image with a non-finite element of gx. */
+int mia_di_resize_pad_bwd_norms(const float* g, float* gx, float* l1, float* l2sq, int N, int C,
+                                int S, int rnd, int top, int left, int* nonfinite, void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);

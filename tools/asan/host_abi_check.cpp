@@ -177,6 +177,44 @@ int main() {
                                    1 << 30, nullptr, nullptr), "ti_smooth_norms H*W overflow");
   expect_error(mia_ti_smooth_norms(dummy, dummy + 32, dummy, 15, dummy, dummy, 1 << 20, 3, 32, 32,
                                    nullptr, nullptr), "ti_smooth_norms N");
+  // input diversity: null / aliased / overlapping buffers, the window's geometry, sizes that
+  // overflow (2 images of 3 × 4 × 4 = 96 floats per buffer: di_a and di_b are disjoint)
+  float di_buf[256];
+  float* di_a = di_buf;
+  float* di_b = di_buf + 128;
+  expect_error(mia_di_resize_pad(nullptr, di_b, 2, 3, 4, 3, 0, 1, nullptr), "di null x");
+  expect_error(mia_di_resize_pad(di_a, nullptr, 2, 3, 4, 3, 0, 1, nullptr), "di null y");
+  expect_error(mia_di_resize_pad(di_a, di_a, 2, 3, 4, 3, 0, 1, nullptr), "di in place");
+  expect_error(mia_di_resize_pad(di_a, di_a + 95, 2, 3, 4, 3, 0, 1, nullptr), "di overlap");
+  expect_error(mia_di_resize_pad(di_a + 1, di_a, 2, 3, 4, 3, 0, 1, nullptr), "di overlap back");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 3, 4, 0, 0, 0, nullptr), "di rnd 0");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 3, 4, 5, 0, 0, nullptr), "di rnd > S");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 3, 4, 3, 2, 0, nullptr), "di top + rnd > S");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 3, 4, 3, 0, 2, nullptr), "di left + rnd > S");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 3, 4, 3, -1, 0, nullptr), "di top < 0");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 3, 4, 3, 0, 2147483647, nullptr),
+               "di left + rnd overflows");
+  expect_error(mia_di_resize_pad(di_a, di_b, 0, 3, 4, 3, 0, 1, nullptr), "di N 0");
+  expect_error(mia_di_resize_pad(di_a, di_b, 1 << 16, 3, 4, 3, 0, 1, nullptr), "di N");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 0, 4, 3, 0, 1, nullptr), "di C 0");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 2, 1 << 15, 3, 0, 1, nullptr), "di C*S*S = 2^31");
+  expect_error(mia_di_resize_pad(di_a, di_b, 2, 1, 1 << 16, 3, 0, 1, nullptr), "di S*S = 2^32");
+  expect_error(mia_di_resize_pad_bwd_norms(nullptr, di_b, dummy, dummy, 2, 3, 4, 3, 0, 1, nullptr,
+                                           nullptr), "di bwd null g");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, nullptr, nullptr, nullptr, 2, 3, 4, 3, 0, 1,
+                                           nullptr, nullptr), "di bwd null gx");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, di_a, dummy, dummy, 2, 3, 4, 3, 0, 1, nullptr,
+                                           nullptr), "di bwd in place");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, di_a + 64, dummy, dummy, 2, 3, 4, 3, 0, 1,
+                                           nullptr, nullptr), "di bwd overlap");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, di_b, dummy, dummy, 2, 3, 4, 5, 0, 0, nullptr,
+                                           nullptr), "di bwd rnd > S");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, di_b, dummy, dummy, 2, 3, 4, 3, 2, 2, nullptr,
+                                           nullptr), "di bwd window");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, di_b, dummy, dummy, 70000, 3, 4, 3, 0, 1,
+                                           nullptr, nullptr), "di bwd N");
+  expect_error(mia_di_resize_pad_bwd_norms(di_a, di_b, dummy, dummy, 2, 3, 46341, 3, 0, 1,
+                                           nullptr, nullptr), "di bwd S*S >= 2^31");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
