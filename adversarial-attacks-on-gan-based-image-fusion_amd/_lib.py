@@ -146,6 +146,9 @@ SIGNATURES = {
     "mia_di_resize_pad": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "mia_di_resize_pad_bwd_norms": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                             P, P]),
+    "mia_si_transform": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, P]),
+    "mia_si_accumulate_norms": (c_int, [P, P, P, P, c_int, c_int64, c_float, c_int, c_float, P,
+                                        P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

@@ -1123,6 +1123,114 @@ __global__ __launch_bounds__(TPB) void mi_update_kernel(float* __restrict__ x,
   }
 }
 
+// ---- scale-invariant and Nesterov attacks (torchattacks SINIFGSM / NIFGSM). Both kernels run on
+// the (slots, N) grid above, but a thread always owns one GROUP of 4 consecutive elements of its
+// image (the last group of a plane that is no multiple of 4 is partial): VEC moves the group as
+// one 16-byte vector, !VEC as guarded scalars. The grid and the element → accumulator mapping are
+// the same either way, so the two forms give the same bits, sums included.
+template <bool VEC>
+__device__ __forceinline__ void ld4(const float* __restrict__ p, int cnt, float (&v)[4]) {
+  if (VEC) {
+    ldv<4>(p, v);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = e < cnt ? p[e] : 0.f;
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void st4(float* __restrict__ p, int cnt, const float (&v)[4]) {
+  if (VEC) {
+    stv<4>(p, v);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < cnt) p[e] = v[e];
+  }
+}
+
+// The input of scale copy i at the Nesterov look-ahead point:
+//   t = m ? x + c·m : x  (c = μ·a);   y = s == 1 ? t : (t + 1)·s − 1  (s = 2^-i)
+// — torchattacks' p / 2^i on p = (x + 1)/2 ∈ [0,1], written in [-1,1] units: towards black. One
+// fp32 rounding per operation; not clamped (as torchattacks). m = nullptr and s = 1: a bit copy.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void si_transform_kernel(const float* __restrict__ x,
+                                                           const float* __restrict__ m,
+                                                           float* __restrict__ y, int64_t plane,
+                                                           float c, float s) {
+#pragma clang fp contract(off)
+  const int64_t base = (int64_t)blockIdx.y * plane, ng = (plane + 3) / 4;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float v[4];
+    ld4<VEC>(x + i0, cnt, v);
+    if (m) {
+      float mv[4];
+      ld4<VEC>(m + i0, cnt, mv);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float look = c * mv[e];
+        v[e] = v[e] + look;
+      }
+    }
+    if (s != 1.f) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float p = v[e] + 1.f;
+        const float ps = p * s;
+        v[e] = ps - 1.f;
+      }
+    }
+    st4<VEC>(y + i0, cnt, v);
+  }
+}
+
+// One scale copy's gradient into the step's accumulator:
+//   v = w·g (w = 2^-i: exact);  r = first ? v : acc + v;  div ≠ 1: r = r / div (IEEE);  acc = r
+// with the per-image partial sums of |r| (quantity 0) and r² (quantity 1). The engine passes
+// div = the number of copies on the last one only. One fp32 rounding per operation; r² enters
+// its sum through an fma, unrounded.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void si_accumulate_norms_kernel(
+    const float* __restrict__ g, float* __restrict__ acc, float* __restrict__ part, int64_t plane,
+    float w, int first, float div, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, ng = (plane + 3) / 4;
+  float a1[4], a2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a1[e] = a2[e] = 0.f;
+  bool bad = false;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float r[4];
+    ld4<VEC>(g + i0, cnt, r);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = w * r[e];
+    if (!first) {
+      float av[4];
+      ld4<VEC>(acc + i0, cnt, av);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = av[e] + r[e];
+    }
+    if (div != 1.f) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = r[e] / div;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {  // the lanes past a partial group hold 0
+      bad |= !__builtin_isfinite(r[e]);
+      a1[e] += fabsf(r[e]);
+      a2[e] = fmaf(r[e], r[e], a2[e]);
+    }
+    st4<VEC>(acc + i0, cnt, r);
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+  block_slot_store<2>(lane_sum<4>(a1), lane_sum<4>(a2), part);
+}
+
 // ---- translation-invariant smoothing (torchattacks TIFGSM): gs = (taps ⊗ taps) ⋆ g per plane,
 // zero padded, with the per-image partial sums of |gs| (quantity 0) and gs² (quantity 1).
 // One block = one TI_T × TI_T output tile of one plane, on a (C·tiles, N) grid: the geometry
@@ -2185,6 +2293,52 @@ extern "C" int mia_di_resize_pad_bwd_norms(const float* g, float* gx, float* l1,
     hipLaunchKernelGGL(di_resize_pad_bwd_norms_kernel<false>, grid, dim3(TPB), 0, st, g, gx,
                        r.part, C, S, rnd, top, left, tiles_x, tiles_y, nonfinite);
   rc = check_launch("di_resize_pad_bwd_norms_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+// s = 2^-i for 0 ≤ i < MIA_SI_MAX_SCALES (NaN fails every comparison)
+static inline bool si_scale_ok(float s) {
+  for (int i = 0; i < MIA_SI_MAX_SCALES; ++i)
+    if (s == ldexpf(1.f, -i)) return true;
+  return false;
+}
+
+extern "C" int mia_si_transform(const float* x, const float* m, float* y, int N, int64_t plane,
+                                float c, float s, void* stream) {
+  MIA_CHECK_ARG(x && y, "null x / y");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(si_scale_ok(s), "s must be 2^-i with 0 <= i < MIA_SI_MAX_SCALES");
+  MIA_CHECK_ARG(__builtin_isfinite(c), "c must be finite");
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(x, y, len) && !(m && di_overlap(m, y, len)),
+                "the inputs and the output must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(y) && (!m || aligned16(m));
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  if (vec) MIA_LAUNCH(si_transform_kernel<true>, grid, dim3(TPB), 0, x, m, y, plane, c, s);
+  MIA_LAUNCH(si_transform_kernel<false>, grid, dim3(TPB), 0, x, m, y, plane, c, s);
+}
+
+extern "C" int mia_si_accumulate_norms(const float* g, float* acc, float* l1, float* l2sq, int N,
+                                       int64_t plane, float w, int first, float div,
+                                       int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(g && acc, "null g / acc");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(si_scale_ok(w), "w must be 2^-i with 0 <= i < MIA_SI_MAX_SCALES");
+  MIA_CHECK_ARG(__builtin_isfinite(div) && div >= 1.f, "div must be finite and >= 1");
+  MIA_CHECK_ARG(!di_overlap(g, acc, (int64_t)N * plane), "g and acc must be distinct buffers");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = plane % 4 == 0 && aligned16(g) && aligned16(acc);
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  RedQ r;
+  int rc = red_begin(r, l1, l2sq, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  if (vec)
+    hipLaunchKernelGGL(si_accumulate_norms_kernel<true>, grid, dim3(TPB), 0, st, g, acc, r.part,
+                       plane, w, first != 0, div, nonfinite);
+  else
+    hipLaunchKernelGGL(si_accumulate_norms_kernel<false>, grid, dim3(TPB), 0, st, g, acc, r.part,
+                       plane, w, first != 0, div, nonfinite);
+  rc = check_launch("si_accumulate_norms_kernel");
   return rc != MIA_OK ? rc : red_finish(r, st);
 }
 

@@ -58,7 +58,10 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     * Input diversity (``di_prob``, ``di_resize_rate``, ``di_schedule``) is shard-local too: the
       draws are a host schedule that every rank computes from ``seed`` alone
       (``pgd.make_di_schedule``; one draw per step serves the whole batch), and the transform
-      acts per image plane, so the output does not depend on the world size."""
+      acts per image plane, so the output does not depend on the world size.
+    * The scale copies and the Nesterov look-ahead (``si_scales``, ``nesterov``) act per image
+      element, and the accumulated gradient's norms are per image: both are shard-local, and the
+      output does not depend on the world size."""
     from . import pgd
     group = group if group is not None else dist.group.WORLD
     world = dist.get_world_size(group)

@@ -2,6 +2,7 @@
 out. Every wrapper validates shapes/dtypes/contiguity on the host before a kernel is launched, so a
 malformed call raises here instead of faulting on the GPU."""
 import ctypes
+import math
 import numbers
 
 import torch
@@ -677,6 +678,64 @@ def di_resize_pad_bwd_norms(g, gx, l1, l2sq, rnd, top, left, nonfinite=None):
     call("mia_di_resize_pad_bwd_norms", ptr(g), ptr(gx), ptr(l1), ptr(l2sq), N, C, S, rnd, top,
          left, ptr(nonfinite), stream())
     return gx
+
+
+SI_MAX_SCALES = 8  # MIA_SI_MAX_SCALES
+
+
+def _si_scale(s, name):
+    """A scale 2^-i with 0 <= i < SI_MAX_SCALES, as a float."""
+    if isinstance(s, bool) or not isinstance(s, numbers.Real):
+        raise ValueError(f"{name} must be a number")
+    s = float(s)
+    if s not in [2.0 ** -i for i in range(SI_MAX_SCALES)]:
+        raise ValueError(f"{name} must be 2^-i with 0 <= i < {SI_MAX_SCALES}")
+    return s
+
+
+def _si_images(x, y, xname, yname):
+    """Shared checks of the scale-invariance pair: distinct non-empty fp32 batches of one shape.
+    Returns (N, elements per image)."""
+    if x is None or x.dim() < 2 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError(f"{xname} must be a non-empty fp32 batch of images")
+    _need(y, x.shape, torch.float32, yname)
+    if y.data_ptr() == x.data_ptr():
+        raise ValueError(f"{xname} and {yname} must be distinct buffers")
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+def si_transform(x, m, y, c, s):
+    """y ← S(x + c·m): the Nesterov look-ahead (m None: none) followed by the scale copy
+    S(t) = (t + 1)·s − 1 for s = 2^-i (s = 1: none) — torchattacks SINIFGSM's p / 2^i in [-1,1]
+    units, towards black (mia_si_transform). x, y (and m): fp32 batches of one shape, y distinct
+    from x and m."""
+    N, plane = _si_images(x, y, "x", "y")
+    if m is not None:
+        _need(m, x.shape, torch.float32, "m")
+        if m.data_ptr() == y.data_ptr():
+            raise ValueError("m and y must be distinct buffers")
+    if isinstance(c, bool) or not isinstance(c, numbers.Real) or not math.isfinite(c):
+        raise ValueError("c must be a finite number")
+    s = _si_scale(s, "s")
+    call("mia_si_transform", ptr(x), ptr(m), ptr(y), N, plane, float(c), s, stream())
+    return y
+
+
+def si_accumulate_norms(g, acc, l1, l2sq, w, first, div=1.0, nonfinite=None):
+    """acc ← (first ? w·g : acc + w·g) / div for w = 2^-i (div = 1: no division), with
+    l1[n] += Σ|acc_n| and l2sq[n] += Σ acc_n² (either may be None) (mia_si_accumulate_norms).
+    g, acc: distinct fp32 batches of one shape."""
+    N, plane = _si_images(g, acc, "g", "acc")
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    w = _si_scale(w, "w")
+    if (isinstance(div, bool) or not isinstance(div, numbers.Real) or not math.isfinite(div)
+            or div < 1):
+        raise ValueError("div must be a finite number >= 1")
+    call("mia_si_accumulate_norms", ptr(g), ptr(acc), ptr(l1), ptr(l2sq), N, plane, w,
+         1 if first else 0, float(div), ptr(nonfinite), stream())
+    return acc
 
 
 def cw_init(x, w):

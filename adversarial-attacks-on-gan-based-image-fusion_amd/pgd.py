@@ -458,6 +458,51 @@ class AttackEngine:
         gs = ws.get("g.ti", x.shape, f32)
         return ops.ti_smooth_norms(gx, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
 
+    def _si_grad_norms(self, x, m, c, n_scales, di, taps, l1, l2sq):
+        """The scale-invariant gradient at the Nesterov look-ahead point (torchattacks SINIFGSM):
+            g = (1/n)·Σ_i 2^-i·∇L(S_i(x_nes)),  x_nes = x + c·m (m None: x),  i = 0 … n − 1,
+        S_i(t) = (t + 1)·2^-i − 1. Per copy: the look-ahead and the scale (ops.si_transform, buffer
+        si.x), the step's resize-and-pad D if ``di`` = (rnd, top, left) (buffer di.x), the
+        objective's gradient at that input (unscaled, as _grad_norms; the targets stay those of
+        x0 and t), added with weight 2^-i — the copy's own Jacobian — into the accumulator
+        (ops.si_accumulate_norms, buffer g.si), which divides by n on the last copy. One D serves
+        every copy of the step, so its adjoint runs once on the accumulated gradient
+        (Dᵀ is linear), then the TI smoothing if ``taps``. The per-image Σ|·| / Σ·² are taken by
+        the last kernel of the chain. Returns the gradient the update kernel reads."""
+        ws, f32 = self.ws, torch.float32
+        n_scales = int(n_scales)
+        if not 1 <= n_scales <= SI_MAX_SCALES:
+            raise ValueError(f"si_scales must be an integer in 1 … {SI_MAX_SCALES}")
+        g = ws.get("g.full", x.shape, f32)
+        acc = ws.get("g.si", x.shape, f32)
+        ends_here = di is None and taps is None
+        for i in range(n_scales):
+            s = 2.0 ** -i
+            xi = x
+            if m is not None or i > 0:  # else a bit copy: the networks read x itself
+                xi = ops.si_transform(x, m, ws.get("si.x", x.shape, f32), c, s)
+            if di is not None:
+                xi = ops.di_resize_pad(xi, ws.get("di.x", x.shape, f32), *di)
+            g_xv, g_enc = self.gradient(xi)
+            ops.grad_assemble(xi, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
+                              1.0 / self.loss_scale, nonfinite=self.nonfinite)
+            last = i == n_scales - 1
+            ops.si_accumulate_norms(g, acc, l1 if last and ends_here else None,
+                                    l2sq if last and ends_here else None, s, i == 0,
+                                    float(n_scales) if last else 1.0, nonfinite=self.nonfinite)
+        if di is not None:
+            gx = ws.get("g.di", x.shape, f32)
+            rnd, top, left = di
+            if taps is None:
+                return ops.di_resize_pad_bwd_norms(acc, gx, l1, l2sq, rnd, top, left,
+                                                   nonfinite=self.nonfinite)
+            acc = ops.di_resize_pad_bwd_norms(acc, gx, None, None, rnd, top, left,
+                                              nonfinite=self.nonfinite)
+        if taps is not None:
+            gs = ws.get("g.ti", x.shape, f32)
+            return ops.ti_smooth_norms(acc, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
+        return acc
+
     def ti_device_taps(self, taps):
         """The 1-D taps (ti_gaussian_taps) rounded once to fp32, on the engine's device."""
         t = torch.as_tensor(taps, dtype=torch.float64).reshape(-1)
@@ -465,14 +510,18 @@ class AttackEngine:
             raise ValueError("ti_taps must hold an odd number of values, 1 … 63")
         return t.to(torch.float32).to(self.G.device).contiguous()
 
-    def step_l2(self, x, a, e, ti_taps=None, di=None):
+    def step_l2(self, x, a, e, ti_taps=None, di=None, si_scales=1):
         """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the step follows the smoothed gradient.
         ``di`` (a make_di_schedule row (rnd, top, left, apply) of host integers): with apply = 1
-        the gradient is Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or None is the plain step."""
+        the gradient is Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or None is the plain step.
+        ``si_scales`` > 1: the gradient is the mean over that many scale copies
+        (_si_grad_norms); 1 is the step without them."""
         sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
         di = _di_row(di)
-        if di is not None:
+        if si_scales != 1:
+            g = self._si_grad_norms(x, None, 0.0, si_scales, di, ti_taps, None, sums[0])
+        elif di is not None:
             g = self._di_grad_norms(x, di, ti_taps, None, sums[0])
         elif ti_taps is None:
             g = self.ws.get("g.full", x.shape, torch.float32)
@@ -483,15 +532,22 @@ class AttackEngine:
         ops.l2_project(x, self.x0, sums[1], _f32(e))
         return x
 
-    def step_mi(self, x, m, momentum, a, e, ti_taps=None, di=None):
+    def step_mi(self, x, m, momentum, a, e, ti_taps=None, di=None, nesterov=False, si_scales=1):
         """One momentum iterative FGSM step on x and the momentum buffer m, both in place.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the TI-FGSM step, on the smoothed
         gradient and its mean. ``di`` (a make_di_schedule row (rnd, top, left, apply) of host
         integers): with apply = 1 the DI-FGSM step, on Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or
-        None is the step without input diversity."""
+        None is the step without input diversity. ``nesterov``: the gradient is taken at the
+        look-ahead point x + c·m, c = momentum·a rounded once to fp32 (torchattacks NIFGSM; not
+        clamped). ``si_scales`` > 1: the gradient is the mean over that many scale copies
+        (torchattacks SINIFGSM, _si_grad_norms). The update rule is the same in every case."""
         l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
         di = _di_row(di)
-        if di is not None:
+        if nesterov or si_scales != 1:
+            c = _f32(_f32(momentum) * _f32(a))
+            g = self._si_grad_norms(x, m if nesterov else None, c, si_scales, di, ti_taps, l1,
+                                    None)
+        elif di is not None:
             g = self._di_grad_norms(x, di, ti_taps, l1, None)
         elif ti_taps is None:
             g = self.ws.get("g.full", x.shape, torch.float32)
@@ -503,7 +559,7 @@ class AttackEngine:
         return x
 
     def run_l2(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None,
-               ti_taps=None, di=None):
+               ti_taps=None, di=None, si_scales=1):
         """L2-ball PGD (torchattacks PGDL2.forward) descending L: per image
         x ← x + a·(−g)/(‖g‖₂ + 1e-10); d = x − x0; x ← clamp(x0 + d·min(e/‖d‖₂, 1), −1, 1), with
         e = 2·eps, a = 2·alpha. ``start_noise``: make_start_noise(shape, seed, "l2"). The norms
@@ -511,23 +567,26 @@ class AttackEngine:
         ``ti_taps`` (1-D taps, ti_gaussian_taps): g is replaced by (taps ⊗ taps) ⋆ g.
         ``di`` (a (steps, 4) schedule, make_di_schedule): step k with apply = 1 follows
         Dₖᵀ ∇L(Dₖ x) (smoothed after the adjoint when ti_taps is given). The schedule is host
-        data fixed before the loop, so an fp16 loss-scale re-run replays the same draws."""
+        data fixed before the loop, so an fp16 loss-scale re-run replays the same draws.
+        ``si_scales`` (1 … SI_MAX_SCALES): every step follows the mean gradient over that many
+        scale copies (_si_grad_norms; one Dₖ serves all copies of step k)."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         rows = _di_rows(di, steps, self.size)
+        n_si = _check_si_scales(si_scales)
         return self._with_rescale(
             lambda: self._run_l2(x0, t, steps, eps, alpha, random_start, start_noise, taps,
-                                 rows), group)
+                                 rows, n_si), group)
 
     def _run_l2(self, x0, t, steps, eps, alpha, random_start, start_noise, ti_taps=None,
-                di=None):
+                di=None, si_scales=1):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
         for k in range(steps):
-            self.step_l2(x, a, e, ti_taps, None if di is None else di[k])
+            self.step_l2(x, a, e, ti_taps, None if di is None else di[k], si_scales)
         return x.clone()
 
     def run_mi(self, x0, t, steps, eps, alpha, momentum=1.0, random_start=False, start_noise=None,
-               group=None, ti_taps=None, di=None):
+               group=None, ti_taps=None, di=None, nesterov=False, si_scales=1):
         """Momentum iterative FGSM (torchattacks MIFGSM.forward) descending L: per image
         ĝ = (−g)/mean|g|; m ← ĝ + μ·m (m = 0 at the start);
         x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1), with e = 2·eps, a = 2·alpha.
@@ -537,20 +596,27 @@ class AttackEngine:
         ``di`` (a (steps, 4) schedule, make_di_schedule): torchattacks DIFGSM (TIFGSM with
         ti_taps) — step k with apply = 1 uses g = Dₖᵀ ∇L(Dₖ x), Dₖ the step's resize-and-pad
         (smoothed after the adjoint when ti_taps is given). The schedule is host data fixed before
-        the loop, so an fp16 loss-scale re-run replays the same draws."""
+        the loop, so an fp16 loss-scale re-run replays the same draws.
+        ``nesterov`` (torchattacks NIFGSM): g is taken at x + μ·a·m instead of at x.
+        ``si_scales`` (1 … SI_MAX_SCALES; torchattacks SINIFGSM's m): g is the mean over that many
+        scale copies, g = (1/n)·Σ_i 2^-i·∇L(S_i(·)), S_i(t) = (t + 1)·2^-i − 1 (_si_grad_norms;
+        one Dₖ serves all copies of step k). Within a step: look-ahead, scale copy, Dₖ, the
+        networks, the accumulation over the copies, one adjoint Dₖᵀ, the smoothing, the update."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         rows = _di_rows(di, steps, self.size)
+        n_si = _check_si_scales(si_scales)
         return self._with_rescale(
             lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                                 taps, rows), group)
+                                 taps, rows, bool(nesterov), n_si), group)
 
     def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                ti_taps=None, di=None):
+                ti_taps=None, di=None, nesterov=False, si_scales=1):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
         m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
         for k in range(steps):
-            self.step_mi(x, m, momentum, a, e, ti_taps, None if di is None else di[k])
+            self.step_mi(x, m, momentum, a, e, ti_taps, None if di is None else di[k], nesterov,
+                         si_scales)
         return x.clone()
 
 
@@ -565,6 +631,18 @@ def _check_images(imgs, size, name):
 
 NORMS = ("linf", "l2", "adam", "l2_cw")
 TI_MAX_KERNEL = 63  # mia_ti_smooth_norms
+SI_MAX_SCALES = ops.SI_MAX_SCALES  # mia_si_transform (torchattacks SINIFGSM's default m is 5)
+
+
+def _check_si_scales(si_scales):
+    """attack()'s / run_*'s ``si_scales``: None (no scale copies) or an integer in
+    1 … SI_MAX_SCALES; returns the number of copies (None → 1)."""
+    if si_scales is None:
+        return 1
+    if (isinstance(si_scales, bool) or not isinstance(si_scales, (int, np.integer))
+            or not 1 <= si_scales <= SI_MAX_SCALES):
+        raise ValueError(f"si_scales must be None or an integer in 1 … {SI_MAX_SCALES}")
+    return int(si_scales)
 
 
 def ti_gaussian_taps(kernlen=15, nsig=3.0):
@@ -708,7 +786,7 @@ def make_start_noise(shape, seed, norm="linf"):
 def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_start=False,
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
-           di_prob=None, di_resize_rate=0.9, di_schedule=None):
+           di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -765,6 +843,26 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             int(S·rate). Rates >= 1 would change the networks' input size and are rejected.
     di_schedule  an explicit host (steps, 4) integer schedule of rows (rnd, top, left, apply)
             instead of the seeded draws (``check_di_schedule``; rnd = S is the identity).
+    si_scales  None (default) or 1: no scale copies. An integer n in 2 … 8 (SI_MAX_SCALES;
+            torchattacks SINIFGSM's default m is 5), with norm='linf' or 'l2': the scale-invariant
+            attack. Every step follows the mean gradient over n scaled copies of the iterate,
+                      g = (1/n)·Σ_i 2^-i·∇L(S_i(x)),  S_i(x) = (x + 1)·2^-i − 1,  i = 0 … n − 1
+            (fused HIP kernels for the copies and their accumulation; n gradient passes per
+            step). S_i is torchattacks' p / 2^i on p = (x + 1)/2 ∈ [0,1]: in these [-1,1] units
+            the copies scale towards black (−1 is the fixed point). Lin et al.'s own code scaled
+            images that were already in [-1,1] and so scaled towards mid-grey; torchattacks is
+            followed here. The whole objective is evaluated at the copy (the targets stay those
+            of x0 and t), as with di_prob. norm='linf' takes the MIFGSM rule (momentum=None means
+            μ = 0), 'l2' the PGDL2 rule. With input diversity ONE resize-and-pad D per step
+            serves all n copies, so the adjoint runs once: g = Dᵀ (1/n)·Σ_i 2^-i·∇L(D S_i(x));
+            the original SI-DIM code drew a fresh D per copy. Order within a step: look-ahead,
+            scale copy, D, the networks, the accumulation, Dᵀ, the TI smoothing, the update.
+    nesterov  False (default). True, with norm='linf' and an explicit momentum μ > 0 only: the
+            torchattacks NIFGSM look-ahead — the step's gradient (or every scale copy) is taken
+            at x + μ·a·m, m the momentum buffer, instead of at x (not clamped, as torchattacks;
+            μ·a is rounded once to fp32). No default μ is guessed: torchattacks' decay defaults
+            differ between NIFGSM / SINIFGSM (1.0) and TIFGSM / DIFGSM (0.0). At step 1 m = 0, so
+            the look-ahead first acts at step 2 (for fgsm() it is a no-op).
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
     Returns the adversarial images on the input's device (fp32), and a dict if return_info.
@@ -784,6 +882,18 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     use_di = di_prob is not None or di_schedule is not None
     if use_di and norm not in ("linf", "l2"):
         raise ValueError("input diversity (DI-FGSM) is implemented for norm='linf' and 'l2' only")
+    n_si = _check_si_scales(si_scales)
+    if si_scales is not None and norm not in ("linf", "l2"):
+        raise ValueError("si_scales (SI-FGSM) is implemented for norm='linf' and 'l2' only")
+    if not isinstance(nesterov, (bool, np.bool_)):
+        raise ValueError("nesterov must be True or False")
+    nesterov = bool(nesterov)
+    if nesterov:
+        if norm != "linf":
+            raise ValueError("nesterov (NI-FGSM) is implemented for norm='linf' only")
+        if momentum is None or not float(momentum) > 0:
+            raise ValueError("nesterov (NI-FGSM) needs an explicit momentum > 0 (torchattacks "
+                             "NIFGSM's default decay is 1.0)")
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
@@ -833,16 +943,17 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf" and (momentum is not None or ti_taps is not None or di is not None):
+    if norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
+                           or n_si > 1):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
                          float(momentum) if momentum is not None else 0.0, random_start, noise,
-                         group=group, ti_taps=ti_taps, di=di)
+                         group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si)
     elif norm == "linf":
         adv = eng.run(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
                       group=group)
     elif norm == "l2":
         adv = eng.run_l2(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
-                         group=group, ti_taps=ti_taps, di=di)
+                         group=group, ti_taps=ti_taps, di=di, si_scales=n_si)
     elif norm == "adam":
         adv = eng.run_adam(x0, t, int(steps), lr=float(lr), group=group)
     else:
@@ -853,13 +964,15 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     momentum=momentum, ti_kernel=ti_kernel, dtype=str(eng.dtype),
                     loss_scale=eng.loss_scale, rescales=eng.rescales, di_prob=di_prob,
                     di_resize_rate=di_resize_rate if di_prob is not None else None,
-                    di_applied=int(di[:, 3].sum()) if di is not None else 0)
+                    di_applied=int(di[:, 3].sum()) if di is not None else 0,
+                    si_scales=si_scales, nesterov=nesterov)
         return adv, info
     return adv
 
 
 def fgsm(net, imgs, eps, **kw):
-    """FGSM = one PGD step with α = ε and no random start."""
+    """FGSM = one PGD step with α = ε and no random start. Every other keyword is forwarded
+    unchanged (nesterov's look-ahead is a no-op at the only step, where the momentum is 0)."""
     kw.pop("alpha", None)
     kw.pop("random_start", None)
     return attack(net, imgs, eps, 1, alpha=eps, random_start=False, **kw)

@@ -470,6 +470,33 @@ int mia_di_resize_pad(const float* x, float* y, int N, int C, int S, int rnd, in
  * bit for bit. nonfinite (NULL or int[N]) is set for an image with a non-finite element of gx. */
 int mia_di_resize_pad_bwd_norms(const float* g, float* gx, float* l1, float* l2sq, int N, int C,
                                 int S, int rnd, int top, int left, int* nonfinite, void* stream);
+/* Scale-invariant and Nesterov attacks (torchattacks SINIFGSM / NIFGSM), images in [-1,1].
+ * The input of scale copy i at the look-ahead point, per element:
+ *   t = m ? x + c·m : x   (c = μ·a; the product rounded, then the sum)
+ *   y = s == 1 ? t : (t + 1)·s − 1   (s = 2^-i)
+ * — torchattacks' p / 2^i on p = (x + 1)/2, so the copies scale towards black (−1 is the fixed
+ * point), not towards mid-grey. y is not clamped (as torchattacks). x, y (and m, or NULL for no
+ * look-ahead): fp32, N images of `plane` elements, y distinct from x and m; s must be 2^-i with
+ * 0 ≤ i < MIA_SI_MAX_SCALES, c finite, N in 1 … 65535, plane < 2^31 (anything else: MIA_EINVAL
+ * before any launch). One fp32 rounding per operation, no contraction; m = NULL with s = 1 copies
+ * x bit for bit. plane % 4 == 0 with 16-byte aligned buffers moves 16-byte vectors, anything
+ * else scalars (the same bits). */
+#define MIA_SI_MAX_SCALES 8
+int mia_si_transform(const float* x, const float* m, float* y, int N, int64_t plane, float c,
+                     float s, void* stream);
+/* One scale copy's gradient into the step's accumulator, with the per-image norms of the result:
+ *   v = w·g (w = 2^-i as above: exact);  r = first ? v : acc + v;  div ≠ 1: r = r / div (IEEE
+ *   division);  acc = r;  l1[n] += Σ|r_n|,  l2sq[n] += Σ r_n²   (fp32 [N], either may be NULL;
+ *   ordered reductions as in mia_grad_assemble_norms).
+ * g, acc: fp32, N images of `plane` elements, distinct buffers; acc is not read when first ≠ 0;
+ * div finite and ≥ 1 (the caller passes the number of copies on the last one, 1 before). A thread
+ * owns 4 consecutive elements of one image whether it moves them as one 16-byte vector
+ * (plane % 4 == 0, 16-byte aligned g / acc) or as scalars, so both forms give the same bits, sums
+ * included; reruns are bit-identical and an image's acc and sums do not depend on the other
+ * images. nonfinite (NULL or int[N]) is set for an image with a non-finite element of r. */
+int mia_si_accumulate_norms(const float* g, float* acc, float* l1, float* l2sq, int N,
+                            int64_t plane, float w, int first, float div, int* nonfinite,
+                            void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);

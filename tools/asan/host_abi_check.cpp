@@ -7,6 +7,7 @@
 // scratch reserve / release cycle, which runs only when a device is present (the GPU box).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -215,6 +216,46 @@ int main() {
                                            nullptr, nullptr), "di bwd N");
   expect_error(mia_di_resize_pad_bwd_norms(di_a, di_b, dummy, dummy, 2, 3, 46341, 3, 0, 1,
                                            nullptr, nullptr), "di bwd S*S >= 2^31");
+  // scale copies / look-ahead: null / aliased / overlapping buffers, scales that are no 2^-i,
+  // sizes (2 images of 48 floats per buffer: di_a and di_b are disjoint)
+  expect_error(mia_si_transform(nullptr, nullptr, di_b, 2, 48, 0.f, 0.5f, nullptr), "si null x");
+  expect_error(mia_si_transform(di_a, nullptr, nullptr, 2, 48, 0.f, 0.5f, nullptr), "si null y");
+  expect_error(mia_si_transform(di_a, nullptr, di_a, 2, 48, 0.f, 0.5f, nullptr), "si in place");
+  expect_error(mia_si_transform(di_a, nullptr, di_a + 95, 2, 48, 0.f, 0.5f, nullptr),
+               "si overlap");
+  expect_error(mia_si_transform(di_a, di_b, di_b, 2, 48, 0.f, 0.5f, nullptr), "si m is y");
+  expect_error(mia_si_transform(di_a, di_b + 1, di_b, 2, 48, 0.f, 0.5f, nullptr),
+               "si m overlaps y");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 48, 0.f, 0.75f, nullptr), "si s 0.75");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 48, 0.f, 2.f, nullptr), "si s 2");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 48, 0.f, 0.f, nullptr), "si s 0");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 48, 0.f, 0.00390625f, nullptr),
+               "si s 2^-8");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 48, 0.f, nanf(""), nullptr), "si s nan");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 48, INFINITY, 0.5f, nullptr), "si c inf");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 0, 48, 0.f, 0.5f, nullptr), "si N 0");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 1 << 16, 48, 0.f, 0.5f, nullptr), "si N");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 0, 0.f, 0.5f, nullptr), "si plane 0");
+  expect_error(mia_si_transform(di_a, nullptr, di_b, 2, 1LL << 31, 0.f, 0.5f, nullptr),
+               "si plane 2^31");
+  expect_error(mia_si_accumulate_norms(nullptr, di_b, dummy, dummy, 2, 48, 0.5f, 0, 1.f, nullptr,
+                                       nullptr), "si acc null g");
+  expect_error(mia_si_accumulate_norms(di_a, nullptr, nullptr, nullptr, 2, 48, 0.5f, 1, 1.f,
+                                       nullptr, nullptr), "si acc null acc");
+  expect_error(mia_si_accumulate_norms(di_a, di_a, dummy, dummy, 2, 48, 0.5f, 0, 1.f, nullptr,
+                                       nullptr), "si acc in place");
+  expect_error(mia_si_accumulate_norms(di_a, di_a + 64, dummy, dummy, 2, 48, 0.5f, 0, 1.f,
+                                       nullptr, nullptr), "si acc overlap");
+  expect_error(mia_si_accumulate_norms(di_a, di_b, dummy, dummy, 2, 48, 3.f, 0, 1.f, nullptr,
+                                       nullptr), "si acc w 3");
+  expect_error(mia_si_accumulate_norms(di_a, di_b, dummy, dummy, 2, 48, 0.5f, 0, 0.5f, nullptr,
+                                       nullptr), "si acc div < 1");
+  expect_error(mia_si_accumulate_norms(di_a, di_b, dummy, dummy, 2, 48, 0.5f, 0, nanf(""),
+                                       nullptr, nullptr), "si acc div nan");
+  expect_error(mia_si_accumulate_norms(di_a, di_b, dummy, dummy, 70000, 48, 0.5f, 0, 1.f,
+                                       nullptr, nullptr), "si acc N");
+  expect_error(mia_si_accumulate_norms(di_a, di_b, dummy, dummy, 2, -1, 0.5f, 0, 1.f, nullptr,
+                                       nullptr), "si acc plane < 0");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
