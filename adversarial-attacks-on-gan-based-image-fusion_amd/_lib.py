@@ -149,6 +149,9 @@ SIGNATURES = {
     "mia_si_transform": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, P]),
     "mia_si_accumulate_norms": (c_int, [P, P, P, P, c_int, c_int64, c_float, c_int, c_float, P,
                                         P]),
+    "mia_vt_neighbor": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, ctypes.c_uint64,
+                                ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]),
+    "mia_vt_combine_norms": (c_int, [P, P, P, P, P, c_int, c_int64, P, P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

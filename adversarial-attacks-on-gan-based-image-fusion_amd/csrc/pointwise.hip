@@ -1231,6 +1231,115 @@ __global__ __launch_bounds__(TPB) void si_accumulate_norms_kernel(
   block_slot_store<2>(lane_sum<4>(a1), lane_sum<4>(a2), part);
 }
 
+// ---- variance-tuned attacks (torchattacks VMIFGSM; Wang & He's VNI with the look-ahead). Both
+// kernels run on the SI kernels' (slots, N) grid, a thread owning one group of 4 consecutive
+// elements of its image, so VEC and the guarded scalars give the same bits. The neighbours' noise
+// is counter-based and stateless: Philox4x32-10 (Salmon et al., Random123) keyed with the attack's
+// seed, the counter (group index within the image, GLOBAL image index, step, sample). One block
+// of 4 words is exactly one group's noise, so an element's value depends on nothing else: not on
+// the batch, the grid, the vector form or the rank that holds the image.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;  // the Weyl sequence of the key
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0;
+  out[1] = c1;
+  out[2] = c2;
+  out[3] = c3;
+}
+
+// One neighbour of the (look-ahead) iterate:
+//   t = m ? x + c·m : x  (as si_transform_kernel);  y = t + r·u,
+//   u = float(2·(bits >> 8) + 1 − 2^24)·2^-24: an odd integer below 2^24 times 2^-24, exact in
+// fp32, symmetric in (−1, 1), never 0 or ±1. One fp32 rounding per operation; not clamped.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void vt_neighbor_kernel(const float* __restrict__ x,
+                                                          const float* __restrict__ m,
+                                                          float* __restrict__ y, int64_t plane,
+                                                          float c, float r, uint32_t k0,
+                                                          uint32_t k1, uint32_t image0,
+                                                          uint32_t step, uint32_t sample) {
+#pragma clang fp contract(off)
+  const int64_t base = (int64_t)blockIdx.y * plane, ng = (plane + 3) / 4;
+  const uint32_t image = image0 + blockIdx.y;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float v[4];
+    ld4<VEC>(x + i0, cnt, v);
+    if (m) {
+      float mv[4];
+      ld4<VEC>(m + i0, cnt, mv);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float look = c * mv[e];
+        v[e] = v[e] + look;
+      }
+    }
+    uint32_t b[4];
+    philox4x32_10((uint32_t)j, image, step, sample, k0, k1, b);  // j < 2^29
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float u = (float)((int)(2u * (b[e] >> 8) + 1u) - (1 << 24)) * 0x1p-24f;
+      const float ru = r * u;
+      v[e] = v[e] + ru;
+    }
+    st4<VEC>(y + i0, cnt, v);
+  }
+}
+
+// The tuned gradient and the next variance term in one pass:
+//   gt = g + v (the OLD v), with the per-image partial sums of |gt|;  gv ? v = gv − g : v stays.
+// One fp32 rounding per operation; the lanes past a partial group hold 0.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void vt_combine_norms_kernel(
+    const float* __restrict__ g, const float* __restrict__ gv, float* __restrict__ v,
+    float* __restrict__ gt, float* __restrict__ part, int64_t plane,
+    int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, ng = (plane + 3) / 4;
+  float a1[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a1[e] = 0.f;
+  bool bad = false;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float gg[4], vv[4], t[4];
+    ld4<VEC>(g + i0, cnt, gg);
+    ld4<VEC>(v + i0, cnt, vv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      t[e] = gg[e] + vv[e];
+      bad |= !__builtin_isfinite(t[e]);
+      a1[e] += fabsf(t[e]);
+    }
+    st4<VEC>(gt + i0, cnt, t);
+    if (gv) {
+      float nv[4];
+      ld4<VEC>(gv + i0, cnt, nv);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        nv[e] = nv[e] - gg[e];
+        bad |= !__builtin_isfinite(nv[e]);
+      }
+      st4<VEC>(v + i0, cnt, nv);
+    }
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+  block_slot_store<1>(lane_sum<4>(a1), 0.f, part);
+}
+
 // ---- translation-invariant smoothing (torchattacks TIFGSM): gs = (taps ⊗ taps) ⋆ g per plane,
 // zero padded, with the per-image partial sums of |gs| (quantity 0) and gs² (quantity 1).
 // One block = one TI_T × TI_T output tile of one plane, on a (C·tiles, N) grid: the geometry
@@ -2339,6 +2448,54 @@ extern "C" int mia_si_accumulate_norms(const float* g, float* acc, float* l1, fl
     hipLaunchKernelGGL(si_accumulate_norms_kernel<false>, grid, dim3(TPB), 0, st, g, acc, r.part,
                        plane, w, first != 0, div, nonfinite);
   rc = check_launch("si_accumulate_norms_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+extern "C" int mia_vt_neighbor(const float* x, const float* m, float* y, int N, int64_t plane,
+                               float c, float r, uint64_t seed, uint32_t image0, uint32_t step,
+                               uint32_t sample, void* stream) {
+  MIA_CHECK_ARG(x && y, "null x / y");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG((uint64_t)image0 + (uint64_t)N <= (1ULL << 32), "image0 + N must be <= 2^32");
+  MIA_CHECK_ARG(__builtin_isfinite(c), "c must be finite");
+  MIA_CHECK_ARG(__builtin_isfinite(r) && r >= 0.f, "r must be finite and >= 0");
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(x, y, len) && !(m && di_overlap(m, y, len)),
+                "the inputs and the output must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(y) && (!m || aligned16(m));
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+  if (vec)
+    MIA_LAUNCH(vt_neighbor_kernel<true>, grid, dim3(TPB), 0, x, m, y, plane, c, r, k0, k1, image0,
+               step, sample);
+  MIA_LAUNCH(vt_neighbor_kernel<false>, grid, dim3(TPB), 0, x, m, y, plane, c, r, k0, k1, image0,
+             step, sample);
+}
+
+extern "C" int mia_vt_combine_norms(const float* g, const float* gv, float* v, float* gt,
+                                    float* l1, int N, int64_t plane, int* nonfinite,
+                                    void* stream) {
+  MIA_CHECK_ARG(g && v && gt, "null g / v / gt");
+  MIA_CHECK_IMAGES(N, plane);
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(g, v, len) && !di_overlap(g, gt, len) && !di_overlap(v, gt, len) &&
+                    !(gv && (di_overlap(gv, g, len) || di_overlap(gv, v, len) ||
+                             di_overlap(gv, gt, len))),
+                "g, gv, v and gt must be distinct buffers");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = plane % 4 == 0 && aligned16(g) && aligned16(v) && aligned16(gt) &&
+                   (!gv || aligned16(gv));
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  RedQ r;
+  int rc = red_begin(r, l1, nullptr, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  if (vec)
+    hipLaunchKernelGGL(vt_combine_norms_kernel<true>, grid, dim3(TPB), 0, st, g, gv, v, gt,
+                       r.part, plane, nonfinite);
+  else
+    hipLaunchKernelGGL(vt_combine_norms_kernel<false>, grid, dim3(TPB), 0, st, g, gv, v, gt,
+                       r.part, plane, nonfinite);
+  rc = check_launch("vt_combine_norms_kernel");
   return rc != MIA_OK ? rc : red_finish(r, st);
 }
 

@@ -6,6 +6,8 @@ whole PGD loop on its shard with no collective in the data path; the only exchan
 ``all_gather_into_tensor`` of the final adversarial images (shards padded to equal size).
 The reference itself is single-GPU (``device = "cuda:0"``, attack_main2.py:843).
 """
+import numbers
+
 import torch
 import torch.distributed as dist
 
@@ -61,7 +63,13 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       acts per image plane, so the output does not depend on the world size.
     * The scale copies and the Nesterov look-ahead (``si_scales``, ``nesterov``) act per image
       element, and the accumulated gradient's norms are per image: both are shard-local, and the
-      output does not depend on the world size."""
+      output does not depend on the world size.
+    * Variance tuning (``vt_samples``, ``vt_beta``): the neighbours' noise is a pure function of
+      (seed, global image index, step, sample, element index), computed in the kernel with no
+      state on host or device. Every shard is attacked with ``vt_first_image`` = the caller's
+      value (default 0, the global index of ``imgs[0]``) + the shard's first row, so each image
+      draws the noise it draws in a single-process attack of the full batch, and the output
+      does not depend on the world size."""
     from . import pgd
     group = group if group is not None else dist.group.WORLD
     world = dist.get_world_size(group)
@@ -78,6 +86,10 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     if random_start:
         noise_norm = "l2" if kw.get("norm", "linf") == "l2" else "linf"
         noise = pgd.make_start_noise(tuple(imgs.shape), seed, noise_norm)[lo:hi]
+    if "vt_samples" in kw or "vt_first_image" in kw:
+        first = kw.get("vt_first_image", 0)
+        if isinstance(first, numbers.Integral) and not isinstance(first, bool):
+            kw = dict(kw, vt_first_image=int(first) + lo)  # anything else: attack() rejects it
     local = pgd.attack(net, imgs[lo:hi], eps, steps, target=tgt, random_start=random_start,
                        seed=seed, start_noise=noise, group=group, **kw)
     return gather_shards(local.to(gather_dev, torch.float32), n, group).to(imgs.device)

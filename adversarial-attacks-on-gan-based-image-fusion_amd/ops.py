@@ -738,6 +738,61 @@ def si_accumulate_norms(g, acc, l1, l2sq, w, first, div=1.0, nonfinite=None):
     return acc
 
 
+def _vt_u32(v, name):
+    """A counter word of the variance-tuning noise: an integer in 0 … 2^32 − 1."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v < 1 << 32:
+        raise ValueError(f"{name} must be an integer in 0 … 2^32 − 1")
+    return int(v)
+
+
+def vt_neighbor(x, m, y, c, r, seed, image0, step, sample):
+    """y ← (x + c·m) + r·u: one neighbour of the Nesterov look-ahead point (m None: of x) for the
+    variance-tuned attack (torchattacks VMIFGSM), u in (−1, 1) from Philox4x32-10 with the key
+    ``seed`` (0 … 2^64 − 1) and the counter (element index / 4, image0 + n, step, sample)
+    (mia_vt_neighbor). Stateless: the noise of an element depends on (seed, global image index,
+    step, sample, element index) only. x, y (and m): fp32 batches of one shape, y distinct from
+    x and m; r finite and >= 0."""
+    N, plane = _si_images(x, y, "x", "y")
+    if m is not None:
+        _need(m, x.shape, torch.float32, "m")
+        if m.data_ptr() == y.data_ptr():
+            raise ValueError("m and y must be distinct buffers")
+    if isinstance(c, bool) or not isinstance(c, numbers.Real) or not math.isfinite(c):
+        raise ValueError("c must be a finite number")
+    if isinstance(r, bool) or not isinstance(r, numbers.Real) or not math.isfinite(r) or r < 0:
+        raise ValueError("r must be a finite number >= 0")
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be an integer in 0 … 2^64 − 1")
+    image0, step, sample = (_vt_u32(v, nm) for v, nm in ((image0, "image0"), (step, "step"),
+                                                         (sample, "sample")))
+    if image0 + N > 1 << 32:
+        raise ValueError("image0 + N must be <= 2^32")
+    call("mia_vt_neighbor", ptr(x), ptr(m), ptr(y), N, plane, float(c), float(r), int(seed),
+         image0, step, sample, stream())
+    return y
+
+
+def vt_combine_norms(g, gv, v, gt, l1, nonfinite=None):
+    """gt ← g + v (the old v) with l1[n] += Σ|gt_n| (l1 may be None), then v ← gv − g (gv None:
+    v stays, the last step) — the tuned gradient and the next variance term of the variance-tuned
+    attack in one pass (mia_vt_combine_norms). g, gv, v, gt: distinct fp32 batches of one shape."""
+    N, plane = _si_images(g, gt, "g", "gt")
+    _need(v, g.shape, torch.float32, "v")
+    bufs = [("g", g), ("v", v), ("gt", gt)]
+    if gv is not None:
+        _need(gv, g.shape, torch.float32, "gv")
+        bufs.append(("gv", gv))
+    for i, (na, a) in enumerate(bufs):
+        for nb, b in bufs[i + 1:]:
+            if a.data_ptr() == b.data_ptr():
+                raise ValueError(f"{na} and {nb} must be distinct buffers")
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    call("mia_vt_combine_norms", ptr(g), ptr(gv), ptr(v), ptr(gt), ptr(l1), N, plane,
+         ptr(nonfinite), stream())
+    return gt
+
+
 def cw_init(x, w):
     _need(w, x.shape, torch.float32, "w")
     call("mia_cw_init", ptr(x), ptr(w), x.numel(), stream())

@@ -17,6 +17,7 @@ together (per-image MSE means; a batch's gradient equals the reference's per-ima
 The loss is never materialised on the device unless ``return_info`` asks for it: PGD needs only
 sign(∇L), so there is no per-step host synchronisation.
 """
+import collections
 import numbers
 
 import numpy as np
@@ -532,7 +533,54 @@ class AttackEngine:
         ops.l2_project(x, self.x0, sums[1], _f32(e))
         return x
 
-    def step_mi(self, x, m, momentum, a, e, ti_taps=None, di=None, nesterov=False, si_scales=1):
+    def _vt_grad(self, x, m, c, si_scales, di):
+        """G(x + c·m) of the variance-tuned step: the step's gradient BEFORE the smoothing and
+        without norms — the plain gradient, Dᵀ ∇L(D ·) with ``di``, the mean over the scale
+        copies with ``si_scales`` > 1 (_grad_norms / _di_grad_norms / _si_grad_norms). Returns a
+        workspace buffer that the next gradient pass overwrites."""
+        if m is not None or si_scales != 1:
+            return self._si_grad_norms(x, m, c, si_scales, di, None, None, None)
+        if di is not None:
+            return self._di_grad_norms(x, di, None, None, None)
+        g = self.ws.get("g.full", x.shape, torch.float32)
+        self._grad_norms(x, g, None, None)
+        return g
+
+    def _vt_grad_norms(self, x, m, c, si_scales, di, taps, l1, vt):
+        """The variance-tuned gradient (torchattacks VMIFGSM) at x_nes = x + c·m (m None: x):
+            g = G(x_nes);  gt = g + v;  gv = (1/N)·Σ_i G(x_nes + r·u_i);  v ← gv − g
+        with v the variance buffer (vt.v, in unscaled gradient units like every gradient here),
+        u_i the step's neighbour noise (ops.vt_neighbor, buffer vt.x) and G as in _vt_grad (one D
+        serves x_nes and all neighbours). g is kept in vt.g and the neighbours' gradients are
+        averaged into vt.gv (ops.si_accumulate_norms, dividing by N on the last one) because G's
+        own buffers are overwritten by the next pass; ops.vt_combine_norms then forms gt (vt.gt)
+        and the new v together. On the last step (``vt.last``) the neighbours are skipped: v is
+        never read again. The TI smoothing, if ``taps``, acts on gt; l1 receives Σ|·| of what
+        the update kernel reads, which is returned."""
+        ws, f32 = self.ws, torch.float32
+        g = ws.get("vt.g", x.shape, f32)
+        g.copy_(self._vt_grad(x, m, c, si_scales, di))
+        v = ws.get("vt.v", x.shape, f32)
+        gv = None
+        if not vt.last:
+            gv = ws.get("vt.gv", x.shape, f32)
+            y = ws.get("vt.x", x.shape, f32)
+            for i in range(vt.samples):
+                ops.vt_neighbor(x, m, y, c, vt.r, vt.seed, vt.image0, vt.step, i)
+                gi = self._vt_grad(y, None, 0.0, si_scales, di)
+                ops.si_accumulate_norms(gi, gv, None, None, 1.0, i == 0,
+                                        float(vt.samples) if i == vt.samples - 1 else 1.0,
+                                        nonfinite=self.nonfinite)
+        gt = ws.get("vt.gt", x.shape, f32)
+        ops.vt_combine_norms(g, gv, v, gt, l1 if taps is None else None,
+                             nonfinite=self.nonfinite)
+        if taps is None:
+            return gt
+        gs = ws.get("g.ti", x.shape, f32)
+        return ops.ti_smooth_norms(gt, taps, gs, l1, None, nonfinite=self.nonfinite)
+
+    def step_mi(self, x, m, momentum, a, e, ti_taps=None, di=None, nesterov=False, si_scales=1,
+                vt=None):
         """One momentum iterative FGSM step on x and the momentum buffer m, both in place.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the TI-FGSM step, on the smoothed
         gradient and its mean. ``di`` (a make_di_schedule row (rnd, top, left, apply) of host
@@ -540,10 +588,16 @@ class AttackEngine:
         None is the step without input diversity. ``nesterov``: the gradient is taken at the
         look-ahead point x + c·m, c = momentum·a rounded once to fp32 (torchattacks NIFGSM; not
         clamped). ``si_scales`` > 1: the gradient is the mean over that many scale copies
-        (torchattacks SINIFGSM, _si_grad_norms). The update rule is the same in every case."""
+        (torchattacks SINIFGSM, _si_grad_norms). ``vt`` (a VtStep: samples, r, seed, image0, step,
+        last): the variance-tuned step (torchattacks VMIFGSM, _vt_grad_norms) on the variance
+        buffer ws "vt.v", with the neighbour noise of step index ``vt.step``; None is the step
+        without it. The update rule is the same in every case."""
         l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
         di = _di_row(di)
-        if nesterov or si_scales != 1:
+        if vt is not None:
+            c = _f32(_f32(momentum) * _f32(a)) if nesterov else 0.0
+            g = self._vt_grad_norms(x, m if nesterov else None, c, si_scales, di, ti_taps, l1, vt)
+        elif nesterov or si_scales != 1:
             c = _f32(_f32(momentum) * _f32(a))
             g = self._si_grad_norms(x, m if nesterov else None, c, si_scales, di, ti_taps, l1,
                                     None)
@@ -586,7 +640,8 @@ class AttackEngine:
         return x.clone()
 
     def run_mi(self, x0, t, steps, eps, alpha, momentum=1.0, random_start=False, start_noise=None,
-               group=None, ti_taps=None, di=None, nesterov=False, si_scales=1):
+               group=None, ti_taps=None, di=None, nesterov=False, si_scales=1, vt_samples=None,
+               vt_beta=1.5, vt_seed=0, vt_first_image=0):
         """Momentum iterative FGSM (torchattacks MIFGSM.forward) descending L: per image
         ĝ = (−g)/mean|g|; m ← ĝ + μ·m (m = 0 at the start);
         x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1), with e = 2·eps, a = 2·alpha.
@@ -601,22 +656,38 @@ class AttackEngine:
         ``si_scales`` (1 … SI_MAX_SCALES; torchattacks SINIFGSM's m): g is the mean over that many
         scale copies, g = (1/n)·Σ_i 2^-i·∇L(S_i(·)), S_i(t) = (t + 1)·2^-i − 1 (_si_grad_norms;
         one Dₖ serves all copies of step k). Within a step: look-ahead, scale copy, Dₖ, the
-        networks, the accumulation over the copies, one adjoint Dₖᵀ, the smoothing, the update."""
+        networks, the accumulation over the copies, one adjoint Dₖᵀ, the smoothing, the update.
+        ``vt_samples`` (1 … VT_MAX_SAMPLES; torchattacks VMIFGSM's N): the variance-tuned attack —
+        the step follows g + v, v the variance term of the previous step (0 at the start):
+        v ← (1/N)·Σ_i G(x_nes + r·u_{k,i}) − G(x_nes), r = fp32(vt_beta)·e in fp32, G the step's
+        gradient before the smoothing (_vt_grad_norms). u_{k,i} is counter-based noise, a pure
+        function of (vt_seed, vt_first_image + n, k, i, element): a loss-scale re-run starts from
+        v = 0 and replays the same noise, and an image's result does not depend on the batch. The
+        last step draws no neighbours."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         rows = _di_rows(di, steps, self.size)
         n_si = _check_si_scales(si_scales)
+        vt = None
+        if vt_samples is not None:
+            vt = (_check_vt_samples(vt_samples), _check_vt_beta(vt_beta),
+                  int(vt_seed) % (1 << 64), _check_vt_first_image(vt_first_image, x0.shape[0]))
         return self._with_rescale(
             lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                                 taps, rows, bool(nesterov), n_si), group)
+                                 taps, rows, bool(nesterov), n_si, vt), group)
 
     def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                ti_taps=None, di=None, nesterov=False, si_scales=1):
+                ti_taps=None, di=None, nesterov=False, si_scales=1, vt=None):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
         x = self._start(x0, t, e, random_start, start_noise)
         m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
+        if vt is not None:
+            n_vt, beta, key, image0 = vt
+            r = _f32(np.float32(beta) * np.float32(e))
+            ops.zero_(self.ws.get("vt.v", x0.shape, torch.float32))
         for k in range(steps):
+            step_vt = None if vt is None else VtStep(n_vt, r, key, image0, k, k == steps - 1)
             self.step_mi(x, m, momentum, a, e, ti_taps, None if di is None else di[k], nesterov,
-                         si_scales)
+                         si_scales, step_vt)
         return x.clone()
 
 
@@ -643,6 +714,42 @@ def _check_si_scales(si_scales):
             or not 1 <= si_scales <= SI_MAX_SCALES):
         raise ValueError(f"si_scales must be None or an integer in 1 … {SI_MAX_SCALES}")
     return int(si_scales)
+
+
+VT_MAX_SAMPLES = 32  # neighbours per step (torchattacks VMIFGSM's default N is 5)
+# The Philox key of the neighbours' noise is (seed + VT_SEED_OFFSET) mod 2^64 ("VMI-FGSM" in
+# ASCII): a stream of its own, like DI_SEED_OFFSET. Step and sample go into the counter.
+VT_SEED_OFFSET = 0x564D492D4647534D
+# One variance-tuned step (step_mi's ``vt``): the number of neighbours, their radius r in [-1,1]
+# units (fp32), the Philox key, the global index of the batch's first image, the 0-based step
+# index of the noise, and whether this is the last step (no neighbours: v is never read again).
+VtStep = collections.namedtuple("VtStep", "samples r seed image0 step last")
+
+
+def _check_vt_samples(vt_samples):
+    """attack()'s / run_mi's ``vt_samples``: an integer in 1 … VT_MAX_SAMPLES."""
+    if (isinstance(vt_samples, bool) or not isinstance(vt_samples, (int, np.integer))
+            or not 1 <= vt_samples <= VT_MAX_SAMPLES):
+        raise ValueError(f"vt_samples must be None or an integer in 1 … {VT_MAX_SAMPLES}")
+    return int(vt_samples)
+
+
+def _check_vt_beta(vt_beta):
+    if (isinstance(vt_beta, (bool, np.bool_)) or not isinstance(vt_beta, numbers.Real)
+            or not np.isfinite(float(vt_beta)) or not float(vt_beta) > 0):
+        raise ValueError("vt_beta must be a finite number > 0")
+    return float(vt_beta)
+
+
+def _check_vt_first_image(vt_first_image, n):
+    """The global index of imgs[0]: an integer >= 0 with vt_first_image + n <= 2^32 (the image
+    word of the noise counter)."""
+    if (isinstance(vt_first_image, (bool, np.bool_))
+            or not isinstance(vt_first_image, (int, np.integer)) or vt_first_image < 0):
+        raise ValueError("vt_first_image must be an integer >= 0")
+    if int(vt_first_image) + int(n) > 1 << 32:
+        raise ValueError("vt_first_image + the batch size must be <= 2^32")
+    return int(vt_first_image)
 
 
 def ti_gaussian_taps(kernlen=15, nsig=3.0):
@@ -786,7 +893,8 @@ def make_start_noise(shape, seed, norm="linf"):
 def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_start=False,
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
-           di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None):
+           di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
+           vt_samples=None, vt_beta=1.5, vt_first_image=0):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -863,6 +971,31 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             μ·a is rounded once to fp32). No default μ is guessed: torchattacks' decay defaults
             differ between NIFGSM / SINIFGSM (1.0) and TIFGSM / DIFGSM (0.0). At step 1 m = 0, so
             the look-ahead first acts at step 2 (for fgsm() it is a no-op).
+    vt_samples  None (default): no variance tuning. An integer N in 1 … 32 (VT_MAX_SAMPLES;
+            torchattacks VMIFGSM's default N is 5), with norm='linf' only: the variance-tuned
+            attack (Wang & He; VNI-FGSM together with nesterov). It takes the MIFGSM rule
+            (momentum=None means μ = 0, as with ti_kernel / di_prob / si_scales; torchattacks
+            VMIFGSM defaults to decay 1.0). Per step k, with v = 0 and m = 0 at the start:
+                      x_nes = x + μ·a·m if nesterov else x
+                      g  = G(x_nes);  gt = g + v;  ĝ = −(W ⋆ gt)/mean|W ⋆ gt|;  m ← ĝ + μ·m
+                      gv = (1/N)·Σ_i G(x_nes + r·u_{k,i}),  r = vt_beta·e,  i = 0 … N − 1
+                      v  ← gv − g;  x ← clamp(x0 + clamp(x + a·sign(m) − x0, −e, e), −1, 1)
+            G is the step's gradient before the smoothing W (none without ti_kernel): the plain
+            gradient, Dᵀ ∇L(D ·) with di_prob and the mean over the scale copies with si_scales,
+            one D per step serving x_nes and all its neighbours — the composition Wang & He
+            report as their strongest. N + 1 gradient passes per step; the last step draws no
+            neighbours (v is never read again), so one step is the plain MI step. The noise
+            u_{k,i} ∈ (−1, 1) is counter-based and stateless (Philox4x32-10 in the HIP kernel): a
+            pure function of (seed, global image index, k, i, element index), keyed with
+            (seed + VT_SEED_OFFSET) mod 2^64. Reruns are bit-identical, there is no host
+            synchronisation, an fp16 loss-scale re-run replays the same draws from v = 0, and an
+            image's result depends on neither the batch nor the world size. The values are not
+            torchattacks' (torch.rand_like on the attack device), the distribution is.
+    vt_beta  torchattacks' beta (default 1.5), finite and > 0: the neighbourhood's radius is
+            vt_beta·eps per pixel (rounded to fp32 once, as fp32(vt_beta)·e).
+    vt_first_image  the global index of imgs[0] (default 0), an integer ≥ 0: image n draws the
+            noise of image vt_first_image + n, so attacking a slice of a batch with its offset
+            gives the rows of the whole batch (``dist.attack_distributed`` passes the shard's).
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
     Returns the adversarial images on the input's device (fp32), and a dict if return_info.
@@ -894,10 +1027,18 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if momentum is None or not float(momentum) > 0:
             raise ValueError("nesterov (NI-FGSM) needs an explicit momentum > 0 (torchattacks "
                              "NIFGSM's default decay is 1.0)")
+    n_vt = None
+    if vt_samples is not None:
+        n_vt = _check_vt_samples(vt_samples)
+        if norm != "linf":
+            raise ValueError("vt_samples (VMI-FGSM) is implemented for norm='linf' only")
+    vt_beta = _check_vt_beta(vt_beta)
+    _check_vt_first_image(vt_first_image, 0)
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
     _check_images(imgs, size, "imgs")
+    vt_first_image = _check_vt_first_image(vt_first_image, imgs.shape[0])
     if target is None:
         target = getattr(net, "default_target", None)
     if target is None:
@@ -943,8 +1084,15 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
-                           or n_si > 1):
+    if norm == "linf" and n_vt is not None:
+        adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
+                         float(momentum) if momentum is not None else 0.0, random_start, noise,
+                         group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si,
+                         vt_samples=n_vt, vt_beta=vt_beta,
+                         vt_seed=(int(seed) + VT_SEED_OFFSET) % (1 << 64),
+                         vt_first_image=vt_first_image)
+    elif norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
+                             or n_si > 1):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
                          float(momentum) if momentum is not None else 0.0, random_start, noise,
                          group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si)
@@ -965,14 +1113,16 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     loss_scale=eng.loss_scale, rescales=eng.rescales, di_prob=di_prob,
                     di_resize_rate=di_resize_rate if di_prob is not None else None,
                     di_applied=int(di[:, 3].sum()) if di is not None else 0,
-                    si_scales=si_scales, nesterov=nesterov)
+                    si_scales=si_scales, nesterov=nesterov, vt_samples=vt_samples,
+                    vt_beta=vt_beta if vt_samples is not None else None)
         return adv, info
     return adv
 
 
 def fgsm(net, imgs, eps, **kw):
     """FGSM = one PGD step with α = ε and no random start. Every other keyword is forwarded
-    unchanged (nesterov's look-ahead is a no-op at the only step, where the momentum is 0)."""
+    unchanged (nesterov's look-ahead is a no-op at the only step, where the momentum is 0; so is
+    vt_samples, whose variance term is 0 there: plain FGSM)."""
     kw.pop("alpha", None)
     kw.pop("random_start", None)
     return attack(net, imgs, eps, 1, alpha=eps, random_start=False, **kw)

@@ -497,6 +497,37 @@ int mia_si_transform(const float* x, const float* m, float* y, int N, int64_t pl
 int mia_si_accumulate_norms(const float* g, float* acc, float* l1, float* l2sq, int N,
                             int64_t plane, float w, int first, float div, int* nonfinite,
                             void* stream);
+/* Variance-tuned attacks (torchattacks VMIFGSM; Wang & He's VNI with the look-ahead), images in
+ * [-1,1]. One neighbour of the (look-ahead) iterate, per element:
+ *   t = m ? x + c·m : x   (as mia_si_transform: the product rounded, then the sum)
+ *   b[0..3] = Philox4x32-10(counter = (j, image0 + n, step, sample),
+ *                           key = (seed & 0xffffffff, seed >> 32))
+ *             j = element index / 4 within the image, n = image within the batch
+ *   u = float(2·(b[e] >> 8) + 1 − 2^24)·2^-24,  e = element index % 4
+ *   y = t + r·u           (the product rounded, then the sum; not clamped, as torchattacks)
+ * Philox4x32-10 is the Random123 definition (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9 / 0xBB67AE85, 10 rounds). u is exact in fp32 (an odd integer below 2^24 times
+ * 2^-24): symmetric in (−1, 1), never 0 or ±1. The noise is a pure function of (seed, image0 + n,
+ * step, sample, element index): nothing stateful on host or device, reruns are bit-identical, and
+ * image n of a batch at image0 equals the same image computed alone with image0 + n.
+ * x, y (and m, or NULL for no look-ahead): fp32, N images of `plane` elements, y distinct from x
+ * and m; N in 1 … 65535, plane < 2^31, image0 + N ≤ 2^32, c finite, r finite and ≥ 0 (anything
+ * else: MIA_EINVAL before any launch). One fp32 rounding per operation, no contraction; r = 0
+ * with m = NULL copies x bit for bit. A thread owns 4 consecutive elements of one image (one
+ * Philox block) whether it moves them as one 16-byte vector (plane % 4 == 0, 16-byte aligned
+ * buffers) or as scalars: the same bits. */
+int mia_vt_neighbor(const float* x, const float* m, float* y, int N, int64_t plane, float c,
+                    float r, uint64_t seed, uint32_t image0, uint32_t step, uint32_t sample,
+                    void* stream);
+/* The tuned gradient and the next variance term in one pass:
+ *   gt = g + v (the OLD v);  l1[n] += Σ|gt_n|   (fp32 [N] or NULL; ordered reduction as in
+ *   mia_si_accumulate_norms);  gv ? v = gv − g : v stays   (gv = NULL: the last step).
+ * g, gv, v, gt: fp32, N images of `plane` elements, distinct buffers. One fp32 rounding per
+ * operation; the vector and scalar forms (as above) give the same bits, the sum included; reruns
+ * are bit-identical and an image's gt, v and sum do not depend on the other images. nonfinite
+ * (NULL or int[N]) is set for an image with a non-finite element of gt or of the new v. */
+int mia_vt_combine_norms(const float* g, const float* gv, float* v, float* gt, float* l1, int N,
+                         int64_t plane, int* nonfinite, void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);
