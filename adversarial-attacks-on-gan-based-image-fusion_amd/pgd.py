@@ -242,11 +242,9 @@ class AttackEngine:
         for it in range(int(max_count)):
             if it == max_count - 1:
                 last.copy_(adv)
-            g_xv, g_enc = self.gradient(adv)
             # the reference's MSEs are batch means (nn.MSELoss over the whole batch, :116): the
             # raw-gradient step scales with 1/N, unlike the sign steps of PGD
-            ops.grad_assemble(adv, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
-                              1.0 / (self.loss_scale * img.shape[0]), nonfinite=self.nonfinite)
+            self._assemble(adv, g, 1.0 / (self.loss_scale * img.shape[0]))
             ops.patch_update(patch, g, img, mask, adv, lo, hi)
         lat, _ = self._encode(last if max_count > 0 else adv, "in.x")
         return adv.clone(), self.G.forward(lat, ws).clone()
@@ -289,13 +287,18 @@ class AttackEngine:
             self.set_loss_scale(self.loss_scale / RESCALE)
             self.rescales += 1
 
+    def _assemble(self, x, g, scale, flag=True, loss=None):
+        """g ← scale·λ·∇_x L at x (fp32 NCHW): gradient(x, loss), then the gradient-assembly
+        kernel on what it left. ``flag``: a non-finite element marks its image in
+        self.nonfinite. Returns g."""
+        g_xv, g_enc = self.gradient(x, loss)
+        return ops.grad_assemble(x, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
+                                 scale, nonfinite=self.nonfinite if flag else None)
+
     def full_gradient(self, x):
         """∇_x L (unscaled, fp32 NCHW) at x."""
         g = self.ws.get("g.full", x.shape, torch.float32)
-        g_xv, g_enc = self.gradient(x)
-        ops.grad_assemble(x, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
-                          1.0 / self.loss_scale)
-        return g.clone()
+        return self._assemble(x, g, 1.0 / self.loss_scale, flag=False).clone()
 
     def objective(self, x, out):
         """Per-image objective at x into out (fp32 [N], +=): forward passes only."""
@@ -317,10 +320,7 @@ class AttackEngine:
 
     def _full_grad(self, x, g, loss=None):
         """g ← ∇_x L (loss-scaled, fp32 NCHW) by the gradient-assembly kernel."""
-        g_xv, g_enc = self.gradient(x, loss)
-        ops.grad_assemble(x, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
-                          nonfinite=self.nonfinite)
-        return g
+        return self._assemble(x, g, 1.0, loss=loss)
 
     def run_adam(self, x0, t, steps, lr=0.01, betas=(0.9, 0.999), eps=1e-8, group=None):
         """``optimize_vgg`` literal mode (interpolation.py:743-843): Adam(lr) on the pixels,
@@ -397,13 +397,7 @@ class AttackEngine:
 
     def _run_pgd(self, x0, t, steps, eps, alpha, random_start, start_noise):
         e, a = 2.0 * eps, 2.0 * alpha
-        self.prepare(x0, t)
-        x = self.ws.get("adv", x0.shape, torch.float32)
-        x.copy_(x0)
-        if random_start:
-            if start_noise is None:
-                raise ValueError("random_start needs start_noise (host-seeded U(-1,1))")
-            ops.random_start(x, x0, start_noise, _f32(e))
+        x = self._start(x0, t, _f32(e), random_start, start_noise)
         for _ in range(steps):
             self.step(x, a, e)
         return x.clone()
@@ -419,90 +413,67 @@ class AttackEngine:
             ops.random_start(x, x0, start_noise, e)
         return x
 
-    def _grad_norms(self, x, g, l1, l2sq):
-        """g ← ∇_x L at x, UNSCALED (scale 1/λ: the normalised steps divide by the gradient's own
-        norm, which must not overflow with λ), with its per-image Σ|g| / Σg² (device-resident)."""
-        g_xv, g_enc = self.gradient(x)
-        ops.grad_assemble_norms(x, self.x0, g_xv, g_enc, g, l1, l2sq, self.pf, ENC_POOL_RES,
-                                self.c_img_o, 1.0 / self.loss_scale, nonfinite=self.nonfinite)
+    def _step_gradient(self, x, m=None, c=0.0, si_scales=1, di=None, taps=None, l1=None,
+                       l2sq=None):
+        """The gradient a normalised step follows, with its per-image Σ|·| (l1) / Σ·² (l2sq, either
+        may be None; device-resident): one chain of stages, each on or off.
 
-    def _ti_grad_norms(self, x, taps, l1, l2sq):
-        """The translation-invariant gradient: ∇_x L at x (unscaled, as _grad_norms) smoothed per
-        plane with taps ⊗ taps (ops.ti_smooth_norms), and the per-image Σ|·| / Σ·² of the
-        SMOOTHED gradient. Returns the smoothed gradient (workspace buffer g.ti)."""
-        g = self.ws.get("g.full", x.shape, torch.float32)
-        g_xv, g_enc = self.gradient(x)
-        ops.grad_assemble(x, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
-                          1.0 / self.loss_scale, nonfinite=self.nonfinite)
-        gs = self.ws.get("g.ti", x.shape, torch.float32)
-        return ops.ti_smooth_norms(g, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
+            per scale copy i:  [x + c·m, S_i → si.x]  [D → di.x]  networks, assemble → g.full
+                               [2^-i·g, /n on the last copy → g.si]
+            once per step:     [Dᵀ → g.di]  [taps ⊗ taps ⋆ → g.ti]
 
-    def _di_grad_norms(self, x, di, taps, l1, l2sq):
-        """The input-diversity gradient g = Dᵀ ∇L(D x) for di = (rnd, top, left) (host integers):
-        xd = D(x) (ops.di_resize_pad, buffer di.x), the objective's gradient AT xd (unscaled, as
-        _grad_norms; the 10·MSE(x0, ·) term and both networks read xd), then its adjoint
-        (ops.di_resize_pad_bwd_norms, buffer g.di). Without taps the per-image Σ|g| / Σg² are
-        taken there; with taps the TI smoothing follows and takes them (buffer g.ti). Returns the
-        gradient the update kernel reads."""
-        rnd, top, left = di
+            g = W ⋆ Dᵀ (1/n)·Σ_i 2^-i·∇L(D S_i(x + c·m)),  S_i(t) = (t + 1)·2^-i − 1,  i = 0 … n − 1
+
+        ``m``: the Nesterov look-ahead (torchattacks NIFGSM), ``si_scales`` = n: the scale copies
+        (SINIFGSM; ops.si_transform does both, and is skipped where it would be a bit copy: the
+        networks then read x itself). ``di`` = (rnd, top, left): the step's resize-and-pad D
+        (ops.di_resize_pad); the 10·MSE(x0, ·) term and both networks read the transformed input,
+        the targets stay those of x0 and t. The gradient is UNSCALED (scale 1/λ: the steps divide
+        by its own norm, which must not overflow with λ). Each copy's gradient is accumulated with
+        weight 2^-i, the copy's own Jacobian (ops.si_accumulate_norms) — also for a look-ahead
+        with a single copy, where w = div = 1. One D serves every copy, so its adjoint runs once,
+        on the accumulated gradient (ops.di_resize_pad_bwd_norms; Dᵀ is linear), then the TI
+        smoothing (ops.ti_smooth_norms). The sums are taken by the last kernel that runs; with no
+        stage after the assembly that is the fused ops.grad_assemble_norms. Returns that kernel's
+        output, the buffer the update kernel reads (the next call overwrites it)."""
         ws, f32 = self.ws, torch.float32
-        xd = ops.di_resize_pad(x, ws.get("di.x", x.shape, f32), rnd, top, left)
-        g = ws.get("g.full", x.shape, f32)
-        g_xv, g_enc = self.gradient(xd)
-        ops.grad_assemble(xd, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
-                          1.0 / self.loss_scale, nonfinite=self.nonfinite)
-        gx = ws.get("g.di", x.shape, f32)
-        if taps is None:
-            return ops.di_resize_pad_bwd_norms(g, gx, l1, l2sq, rnd, top, left,
-                                               nonfinite=self.nonfinite)
-        ops.di_resize_pad_bwd_norms(g, gx, None, None, rnd, top, left, nonfinite=self.nonfinite)
-        gs = ws.get("g.ti", x.shape, f32)
-        return ops.ti_smooth_norms(gx, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
-
-    def _si_grad_norms(self, x, m, c, n_scales, di, taps, l1, l2sq):
-        """The scale-invariant gradient at the Nesterov look-ahead point (torchattacks SINIFGSM):
-            g = (1/n)·Σ_i 2^-i·∇L(S_i(x_nes)),  x_nes = x + c·m (m None: x),  i = 0 … n − 1,
-        S_i(t) = (t + 1)·2^-i − 1. Per copy: the look-ahead and the scale (ops.si_transform, buffer
-        si.x), the step's resize-and-pad D if ``di`` = (rnd, top, left) (buffer di.x), the
-        objective's gradient at that input (unscaled, as _grad_norms; the targets stay those of
-        x0 and t), added with weight 2^-i — the copy's own Jacobian — into the accumulator
-        (ops.si_accumulate_norms, buffer g.si), which divides by n on the last copy. One D serves
-        every copy of the step, so its adjoint runs once on the accumulated gradient
-        (Dᵀ is linear), then the TI smoothing if ``taps``. The per-image Σ|·| / Σ·² are taken by
-        the last kernel of the chain. Returns the gradient the update kernel reads."""
-        ws, f32 = self.ws, torch.float32
-        n_scales = int(n_scales)
-        if not 1 <= n_scales <= SI_MAX_SCALES:
+        n = int(si_scales)
+        if not 1 <= n <= SI_MAX_SCALES:
             raise ValueError(f"si_scales must be an integer in 1 … {SI_MAX_SCALES}")
-        g = ws.get("g.full", x.shape, f32)
-        acc = ws.get("g.si", x.shape, f32)
-        ends_here = di is None and taps is None
-        for i in range(n_scales):
-            s = 2.0 ** -i
+        accumulate = m is not None or si_scales != 1
+        last_stage = ("ti" if taps is not None else "di" if di is not None
+                      else "si" if accumulate else "full")
+
+        def sums(stage, last_copy=True):
+            return (l1, l2sq) if stage == last_stage and last_copy else (None, None)
+
+        flag = self.nonfinite
+        g = out = ws.get("g.full", x.shape, f32)
+        for i in range(n):
             xi = x
-            if m is not None or i > 0:  # else a bit copy: the networks read x itself
-                xi = ops.si_transform(x, m, ws.get("si.x", x.shape, f32), c, s)
+            if m is not None or i > 0:
+                xi = ops.si_transform(x, m, ws.get("si.x", x.shape, f32), c, 2.0 ** -i)
             if di is not None:
                 xi = ops.di_resize_pad(xi, ws.get("di.x", x.shape, f32), *di)
-            g_xv, g_enc = self.gradient(xi)
-            ops.grad_assemble(xi, self.x0, g_xv, g_enc, g, self.pf, ENC_POOL_RES, self.c_img_o,
-                              1.0 / self.loss_scale, nonfinite=self.nonfinite)
-            last = i == n_scales - 1
-            ops.si_accumulate_norms(g, acc, l1 if last and ends_here else None,
-                                    l2sq if last and ends_here else None, s, i == 0,
-                                    float(n_scales) if last else 1.0, nonfinite=self.nonfinite)
+            if last_stage == "full":
+                g_xv, g_enc = self.gradient(xi)
+                ops.grad_assemble_norms(xi, self.x0, g_xv, g_enc, g, *sums("full"), self.pf,
+                                        ENC_POOL_RES, self.c_img_o, 1.0 / self.loss_scale,
+                                        nonfinite=flag)
+            else:
+                self._assemble(xi, g, 1.0 / self.loss_scale)
+            if accumulate:
+                last = i == n - 1
+                out = ops.si_accumulate_norms(g, ws.get("g.si", x.shape, f32), *sums("si", last),
+                                              2.0 ** -i, i == 0, float(n) if last else 1.0,
+                                              nonfinite=flag)
         if di is not None:
-            gx = ws.get("g.di", x.shape, f32)
-            rnd, top, left = di
-            if taps is None:
-                return ops.di_resize_pad_bwd_norms(acc, gx, l1, l2sq, rnd, top, left,
-                                                   nonfinite=self.nonfinite)
-            acc = ops.di_resize_pad_bwd_norms(acc, gx, None, None, rnd, top, left,
-                                              nonfinite=self.nonfinite)
+            out = ops.di_resize_pad_bwd_norms(out, ws.get("g.di", x.shape, f32), *sums("di"), *di,
+                                              nonfinite=flag)
         if taps is not None:
-            gs = ws.get("g.ti", x.shape, f32)
-            return ops.ti_smooth_norms(acc, taps, gs, l1, l2sq, nonfinite=self.nonfinite)
-        return acc
+            out = ops.ti_smooth_norms(out, taps, ws.get("g.ti", x.shape, f32), *sums("ti"),
+                                      nonfinite=flag)
+        return out
 
     def ti_device_taps(self, taps):
         """The 1-D taps (ti_gaussian_taps) rounded once to fp32, on the engine's device."""
@@ -515,42 +486,23 @@ class AttackEngine:
         """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the step follows the smoothed gradient.
         ``di`` (a make_di_schedule row (rnd, top, left, apply) of host integers): with apply = 1
-        the gradient is Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or None is the plain step.
-        ``si_scales`` > 1: the gradient is the mean over that many scale copies
-        (_si_grad_norms); 1 is the step without them."""
+        the gradient is Dᵀ ∇L(D x); apply = 0 or None is the plain step.
+        ``si_scales`` > 1: the gradient is the mean over that many scale copies; 1 is the step
+        without them (_step_gradient for all three)."""
+        # sums: Σg², Σ(adv − x0)² per image
         sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
-        di = _di_row(di)
-        if si_scales != 1:
-            g = self._si_grad_norms(x, None, 0.0, si_scales, di, ti_taps, None, sums[0])
-        elif di is not None:
-            g = self._di_grad_norms(x, di, ti_taps, None, sums[0])
-        elif ti_taps is None:
-            g = self.ws.get("g.full", x.shape, torch.float32)
-            self._grad_norms(x, g, None, sums[0])  # sums: Σg², Σ(adv − x0)² per image
-        else:
-            g = self._ti_grad_norms(x, ti_taps, None, sums[0])
+        g = self._step_gradient(x, si_scales=si_scales, di=_di_row(di), taps=ti_taps,
+                                l2sq=sums[0])
         ops.l2_step(x, self.x0, g, sums[0], sums[1], _f32(a), nonfinite=self.nonfinite)
         ops.l2_project(x, self.x0, sums[1], _f32(e))
         return x
-
-    def _vt_grad(self, x, m, c, si_scales, di):
-        """G(x + c·m) of the variance-tuned step: the step's gradient BEFORE the smoothing and
-        without norms — the plain gradient, Dᵀ ∇L(D ·) with ``di``, the mean over the scale
-        copies with ``si_scales`` > 1 (_grad_norms / _di_grad_norms / _si_grad_norms). Returns a
-        workspace buffer that the next gradient pass overwrites."""
-        if m is not None or si_scales != 1:
-            return self._si_grad_norms(x, m, c, si_scales, di, None, None, None)
-        if di is not None:
-            return self._di_grad_norms(x, di, None, None, None)
-        g = self.ws.get("g.full", x.shape, torch.float32)
-        self._grad_norms(x, g, None, None)
-        return g
 
     def _vt_grad_norms(self, x, m, c, si_scales, di, taps, l1, vt):
         """The variance-tuned gradient (torchattacks VMIFGSM) at x_nes = x + c·m (m None: x):
             g = G(x_nes);  gt = g + v;  gv = (1/N)·Σ_i G(x_nes + r·u_i);  v ← gv − g
         with v the variance buffer (vt.v, in unscaled gradient units like every gradient here),
-        u_i the step's neighbour noise (ops.vt_neighbor, buffer vt.x) and G as in _vt_grad (one D
+        u_i the step's neighbour noise (ops.vt_neighbor, buffer vt.x) and G the step's gradient
+        BEFORE the smoothing and without norms (_step_gradient with no taps and no sums; one D
         serves x_nes and all neighbours). g is kept in vt.g and the neighbours' gradients are
         averaged into vt.gv (ops.si_accumulate_norms, dividing by N on the last one) because G's
         own buffers are overwritten by the next pass; ops.vt_combine_norms then forms gt (vt.gt)
@@ -559,7 +511,7 @@ class AttackEngine:
         the update kernel reads, which is returned."""
         ws, f32 = self.ws, torch.float32
         g = ws.get("vt.g", x.shape, f32)
-        g.copy_(self._vt_grad(x, m, c, si_scales, di))
+        g.copy_(self._step_gradient(x, m, c, si_scales, di))
         v = ws.get("vt.v", x.shape, f32)
         gv = None
         if not vt.last:
@@ -567,7 +519,7 @@ class AttackEngine:
             y = ws.get("vt.x", x.shape, f32)
             for i in range(vt.samples):
                 ops.vt_neighbor(x, m, y, c, vt.r, vt.seed, vt.image0, vt.step, i)
-                gi = self._vt_grad(y, None, 0.0, si_scales, di)
+                gi = self._step_gradient(y, si_scales=si_scales, di=di)
                 ops.si_accumulate_norms(gi, gv, None, None, 1.0, i == 0,
                                         float(vt.samples) if i == vt.samples - 1 else 1.0,
                                         nonfinite=self.nonfinite)
@@ -584,30 +536,24 @@ class AttackEngine:
         """One momentum iterative FGSM step on x and the momentum buffer m, both in place.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the TI-FGSM step, on the smoothed
         gradient and its mean. ``di`` (a make_di_schedule row (rnd, top, left, apply) of host
-        integers): with apply = 1 the DI-FGSM step, on Dᵀ ∇L(D x) (_di_grad_norms); apply = 0 or
-        None is the step without input diversity. ``nesterov``: the gradient is taken at the
-        look-ahead point x + c·m, c = momentum·a rounded once to fp32 (torchattacks NIFGSM; not
-        clamped). ``si_scales`` > 1: the gradient is the mean over that many scale copies
-        (torchattacks SINIFGSM, _si_grad_norms). ``vt`` (a VtStep: samples, r, seed, image0, step,
+        integers): with apply = 1 the DI-FGSM step, on Dᵀ ∇L(D x); apply = 0 or None is the step
+        without input diversity. ``nesterov``: the gradient is taken at the look-ahead point
+        x + c·m, c = momentum·a rounded once to fp32 (torchattacks NIFGSM; not clamped).
+        ``si_scales`` > 1: the gradient is the mean over that many scale copies (torchattacks
+        SINIFGSM; _step_gradient for all four). ``vt`` (a VtStep: samples, r, seed, image0, step,
         last): the variance-tuned step (torchattacks VMIFGSM, _vt_grad_norms) on the variance
         buffer ws "vt.v", with the neighbour noise of step index ``vt.step``; None is the step
         without it. The update rule is the same in every case."""
         l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
         di = _di_row(di)
-        if vt is not None:
-            c = _f32(_f32(momentum) * _f32(a)) if nesterov else 0.0
-            g = self._vt_grad_norms(x, m if nesterov else None, c, si_scales, di, ti_taps, l1, vt)
-        elif nesterov or si_scales != 1:
-            c = _f32(_f32(momentum) * _f32(a))
-            g = self._si_grad_norms(x, m if nesterov else None, c, si_scales, di, ti_taps, l1,
-                                    None)
-        elif di is not None:
-            g = self._di_grad_norms(x, di, ti_taps, l1, None)
-        elif ti_taps is None:
-            g = self.ws.get("g.full", x.shape, torch.float32)
-            self._grad_norms(x, g, l1, None)
+        # No kernel reads c without the look-ahead buffer; the variance-tuned step then passes 0
+        # where the others pass μ·a, and the launch trace pins both (tests/test_step_trace_host.py)
+        c = _f32(_f32(momentum) * _f32(a)) if nesterov or vt is None else 0.0
+        look = m if nesterov else None
+        if vt is None:
+            g = self._step_gradient(x, look, c, si_scales, di, ti_taps, l1)
         else:
-            g = self._ti_grad_norms(x, ti_taps, l1, None)
+            g = self._vt_grad_norms(x, look, c, si_scales, di, ti_taps, l1, vt)
         ops.mi_update(x, self.x0, g, l1, m, _f32(momentum), _f32(a), _f32(e),
                       nonfinite=self.nonfinite)
         return x
@@ -623,7 +569,7 @@ class AttackEngine:
         Dₖᵀ ∇L(Dₖ x) (smoothed after the adjoint when ti_taps is given). The schedule is host
         data fixed before the loop, so an fp16 loss-scale re-run replays the same draws.
         ``si_scales`` (1 … SI_MAX_SCALES): every step follows the mean gradient over that many
-        scale copies (_si_grad_norms; one Dₖ serves all copies of step k)."""
+        scale copies (_step_gradient; one Dₖ serves all copies of step k)."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         rows = _di_rows(di, steps, self.size)
         n_si = _check_si_scales(si_scales)
@@ -654,7 +600,7 @@ class AttackEngine:
         the loop, so an fp16 loss-scale re-run replays the same draws.
         ``nesterov`` (torchattacks NIFGSM): g is taken at x + μ·a·m instead of at x.
         ``si_scales`` (1 … SI_MAX_SCALES; torchattacks SINIFGSM's m): g is the mean over that many
-        scale copies, g = (1/n)·Σ_i 2^-i·∇L(S_i(·)), S_i(t) = (t + 1)·2^-i − 1 (_si_grad_norms;
+        scale copies, g = (1/n)·Σ_i 2^-i·∇L(S_i(·)), S_i(t) = (t + 1)·2^-i − 1 (_step_gradient;
         one Dₖ serves all copies of step k). Within a step: look-ahead, scale copy, Dₖ, the
         networks, the accumulation over the copies, one adjoint Dₖᵀ, the smoothing, the update.
         ``vt_samples`` (1 … VT_MAX_SAMPLES; torchattacks VMIFGSM's N): the variance-tuned attack —
@@ -1084,18 +1030,14 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf" and n_vt is not None:
+    if norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
+                           or n_si > 1 or n_vt is not None):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
                          float(momentum) if momentum is not None else 0.0, random_start, noise,
                          group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si,
                          vt_samples=n_vt, vt_beta=vt_beta,
                          vt_seed=(int(seed) + VT_SEED_OFFSET) % (1 << 64),
                          vt_first_image=vt_first_image)
-    elif norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
-                             or n_si > 1):
-        adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
-                         float(momentum) if momentum is not None else 0.0, random_start, noise,
-                         group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si)
     elif norm == "linf":
         adv = eng.run(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
                       group=group)

@@ -119,8 +119,8 @@ def test_signatures_and_distributed_docs():
         q = inspect.signature(getattr(AttackEngine, name)).parameters
         assert q["si_scales"].default == 1, name
         assert ("nesterov" in q) == name.endswith("_mi"), name
-    assert list(inspect.signature(AttackEngine._si_grad_norms).parameters) == [
-        "self", "x", "m", "c", "n_scales", "di", "taps", "l1", "l2sq"]
+    assert list(inspect.signature(AttackEngine._step_gradient).parameters) == [
+        "self", "x", "m", "c", "si_scales", "di", "taps", "l1", "l2sq"]
     assert any(q.kind is inspect.Parameter.VAR_KEYWORD
                for q in inspect.signature(fgsm).parameters.values())
     for kwd in ("si_scales", "nesterov", "world size"):

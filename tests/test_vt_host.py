@@ -159,8 +159,8 @@ def test_signatures_constants_and_docs():
                       "start_noise", "group", "ti_taps", "di", "nesterov", "si_scales"]
     assert q[14:] == ["vt_samples", "vt_beta", "vt_seed", "vt_first_image"]
     assert inspect.signature(AttackEngine.run_mi).parameters["vt_samples"].default is None
-    assert list(inspect.signature(AttackEngine._si_grad_norms).parameters) == [
-        "self", "x", "m", "c", "n_scales", "di", "taps", "l1", "l2sq"]
+    assert list(inspect.signature(AttackEngine._step_gradient).parameters) == [
+        "self", "x", "m", "c", "si_scales", "di", "taps", "l1", "l2sq"]
     assert pgd.VtStep._fields == ("samples", "r", "seed", "image0", "step", "last")
     assert any(k.kind is inspect.Parameter.VAR_KEYWORD
                for k in inspect.signature(fgsm).parameters.values())
