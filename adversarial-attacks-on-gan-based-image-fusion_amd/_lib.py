@@ -152,6 +152,10 @@ SIGNATURES = {
     "mia_vt_neighbor": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, ctypes.c_uint64,
                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]),
     "mia_vt_combine_norms": (c_int, [P, P, P, P, P, c_int, c_int64, P, P]),
+    "mia_apgd_update": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float,
+                                P, P]),
+    "mia_apgd_decide": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
+    "mia_apgd_apply": (c_int, [P, P, P, P, P, c_int, c_int64, P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

@@ -1340,6 +1340,154 @@ __global__ __launch_bounds__(TPB) void vt_combine_norms_kernel(
   block_slot_store<1>(lane_sum<4>(a1), 0.f, part);
 }
 
+// ---- Auto-PGD (Croce & Hein 2020; torchattacks APGD.attack_single_run, norm = 'Linf') on
+// cost = −L. Three kernels per step. The update and the copies run on the SI kernels' (slots, N)
+// grid, a thread owning one group of 4 consecutive elements of its image, so VEC and the guarded
+// scalars give the same bits. Per-image state is only ever READ by those two (eta, action); it is
+// written by the decision kernel, one thread per image, in a launch of its own — no block reads
+// what another block of its launch rewrites.
+//
+// The momentum step with a per-image step size eta[n], torchattacks' bound form:
+//   d = x − x_old;  x_old = x
+//   z = clamp(min(max(x − eta[n]·sign(g), x0 − e), x0 + e), lo, hi)
+//   x = clamp(min(max((x + (z − x)·a) + d·(1 − a), x0 − e), x0 + e), lo, hi)
+// One fp32 rounding per operation (1 − a too); sign(0) = sign(NaN) = 0.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void apgd_update_kernel(float* __restrict__ x,
+                                                          float* __restrict__ x_old,
+                                                          const float* __restrict__ x0,
+                                                          const float* __restrict__ g,
+                                                          const float* __restrict__ eta,
+                                                          int64_t plane, float a, float e, float lo,
+                                                          float hi, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, ng = (plane + 3) / 4;
+  const float step = eta[n];
+  const float b = 1.f - a;
+  bool bad = false;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float xv[4], ov[4], x0v[4], gg[4];
+    ld4<VEC>(x + i0, cnt, xv);
+    ld4<VEC>(x_old + i0, cnt, ov);
+    ld4<VEC>(x0 + i0, cnt, x0v);
+    ld4<VEC>(g + i0, cnt, gg);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // the lanes past a partial group hold 0 and are not stored
+      bad |= !__builtin_isfinite(gg[k]);
+      const float d = xv[k] - ov[k];
+      ov[k] = xv[k];
+      const float sg = gg[k] > 0.f ? 1.f : (gg[k] < 0.f ? -1.f : 0.f);
+      const float lb = x0v[k] - e;
+      const float ub = x0v[k] + e;
+      const float t = xv[k] - step * sg;  // eta·(±1 | 0) is exact
+      const float z = fminf(fmaxf(fminf(fmaxf(t, lb), ub), lo), hi);
+      const float zx = z - xv[k];
+      const float za = zx * a;
+      const float s1 = xv[k] + za;
+      const float db = d * b;
+      const float s2 = s1 + db;
+      xv[k] = fminf(fmaxf(fminf(fmaxf(s2, lb), ub), lo), hi);
+    }
+    st4<VEC>(x_old + i0, cnt, ov);
+    st4<VEC>(x + i0, cnt, xv);
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+}
+
+// Per-image state of the step-size control: fs = fp32 (4, N) rows eta, L_best, L_prev, L_check;
+// is = int32 (3, N) rows n_dec, reduced, best_step.
+enum { APGD_ETA = 0, APGD_LBEST = 1, APGD_LPREV = 2, APGD_LCHECK = 3 };
+enum { APGD_NDEC = 0, APGD_REDUCED = 1, APGD_BESTSTEP = 2 };
+
+// One thread per image. step = 0, the start: the state is initialised from L(x) and eta0, and the
+// action is SAVE. step = i + 1, after update i: with L = loss[n],
+//   L < L_prev: n_dec += 1;  L_prev = L;  L < L_best: L_best = L, best_step = step, SAVE
+//   at a checkpoint: flag = n_dec <= thr || (reduced == 0 && L_check <= L_best);
+//                    reduced = flag;  L_check = L_best;  n_dec = 0;  flag: eta /= 2, RESTORE
+// A NaN objective fails every comparison: never a decrease, never the best. The row (L, eta) is
+// appended to the history.
+__global__ void apgd_decide_kernel(const float* __restrict__ loss, float* __restrict__ fs,
+                                   int* __restrict__ is, int* __restrict__ action,
+                                   float* __restrict__ hist_loss, float* __restrict__ hist_eta,
+                                   int N, int step, int checkpoint, int thr, float eta0) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const float L = loss[n];
+  float eta;
+  int act = 0;
+  if (step == 0) {
+    eta = eta0;
+    fs[APGD_LBEST * N + n] = L;
+    fs[APGD_LPREV * N + n] = L;
+    fs[APGD_LCHECK * N + n] = L;
+    is[APGD_NDEC * N + n] = 0;
+    is[APGD_REDUCED * N + n] = 1;
+    is[APGD_BESTSTEP * N + n] = 0;
+    act = MIA_APGD_SAVE;
+  } else {
+    eta = fs[APGD_ETA * N + n];
+    float best = fs[APGD_LBEST * N + n];
+    int ndec = is[APGD_NDEC * N + n];
+    if (L < fs[APGD_LPREV * N + n]) ++ndec;
+    fs[APGD_LPREV * N + n] = L;
+    if (L < best) {
+      best = L;
+      fs[APGD_LBEST * N + n] = L;
+      is[APGD_BESTSTEP * N + n] = step;
+      act |= MIA_APGD_SAVE;
+    }
+    if (checkpoint) {
+      const bool flag = ndec <= thr ||
+                        (is[APGD_REDUCED * N + n] == 0 && fs[APGD_LCHECK * N + n] <= best);
+      is[APGD_REDUCED * N + n] = flag ? 1 : 0;
+      fs[APGD_LCHECK * N + n] = best;
+      ndec = 0;
+      if (flag) {
+        eta = eta / 2.f;
+        act |= MIA_APGD_RESTORE;
+      }
+    }
+    is[APGD_NDEC * N + n] = ndec;
+  }
+  fs[APGD_ETA * N + n] = eta;
+  action[n] = act;
+  hist_loss[n] = L;
+  hist_eta[n] = eta;
+}
+
+// The whole-image copies the decision asked for, per image n (action[n] was written by an earlier
+// launch): SAVE: x_best = x, g_best = g;  RESTORE without SAVE: x = x_best, g = g_best. With both
+// bits the best point IS the iterate, so the restore is the identity and only the save runs.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void apgd_apply_kernel(float* __restrict__ x,
+                                                         float* __restrict__ g,
+                                                         float* __restrict__ x_best,
+                                                         float* __restrict__ g_best,
+                                                         const int* __restrict__ action,
+                                                         int64_t plane) {
+  const int act = action[blockIdx.y];
+  if (!(act & (MIA_APGD_SAVE | MIA_APGD_RESTORE))) return;
+  const bool save = act & MIA_APGD_SAVE;
+  const float* sx = save ? x : x_best;
+  const float* sg = save ? g : g_best;
+  float* dx = save ? x_best : x;
+  float* dg = save ? g_best : g;
+  const int64_t base = (int64_t)blockIdx.y * plane, ng = (plane + 3) / 4;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float v[4], w[4];
+    ld4<VEC>(sx + i0, cnt, v);
+    ld4<VEC>(sg + i0, cnt, w);
+    st4<VEC>(dx + i0, cnt, v);
+    st4<VEC>(dg + i0, cnt, w);
+  }
+}
+
 // ---- translation-invariant smoothing (torchattacks TIFGSM): gs = (taps ⊗ taps) ⋆ g per plane,
 // zero padded, with the per-image partial sums of |gs| (quantity 0) and gs² (quantity 1).
 // One block = one TI_T × TI_T output tile of one plane, on a (C·tiles, N) grid: the geometry
@@ -2497,6 +2645,68 @@ extern "C" int mia_vt_combine_norms(const float* g, const float* gv, float* v, f
                        r.part, plane, nonfinite);
   rc = check_launch("vt_combine_norms_kernel");
   return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+extern "C" int mia_apgd_update(float* x, float* x_old, const float* x0, const float* g,
+                               const float* eta, int N, int64_t plane, float a, float e, float lo,
+                               float hi, int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(x && x_old && x0 && g && eta, "null argument");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(a > 0.f && a <= 1.f, "the momentum weight a must be in (0, 1]");
+  MIA_CHECK_ARG(e > 0.f && __builtin_isfinite(e) && lo <= hi, "need a finite e > 0 and lo <= hi");
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(x, x_old, len) && !di_overlap(x, x0, len) && !di_overlap(x, g, len) &&
+                    !di_overlap(x_old, x0, len) && !di_overlap(x_old, g, len),
+                "x, x_old, x0 and g must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(x_old) && aligned16(x0) &&
+                   aligned16(g);
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  if (vec)
+    MIA_LAUNCH(apgd_update_kernel<true>, grid, dim3(TPB), 0, x, x_old, x0, g, eta, plane, a, e, lo,
+               hi, nonfinite);
+  MIA_LAUNCH(apgd_update_kernel<false>, grid, dim3(TPB), 0, x, x_old, x0, g, eta, plane, a, e, lo,
+             hi, nonfinite);
+}
+
+extern "C" int mia_apgd_decide(const float* loss, float* fstate, int* istate, int* action,
+                               float* hist_loss, float* hist_eta, int N, int step, int checkpoint,
+                               int thr, float eta0, void* stream) {
+  MIA_CHECK_ARG(loss && fstate && istate && action && hist_loss && hist_eta, "null argument");
+  MIA_CHECK_ARG(N > 0 && N <= 65535, "N must be in 1 … 65535");
+  MIA_CHECK_ARG(step >= 0, "step must be >= 0");
+  MIA_CHECK_ARG(checkpoint == 0 || checkpoint == 1, "checkpoint must be 0 or 1");
+  MIA_CHECK_ARG(thr >= 0, "the threshold must be >= 0");
+  MIA_CHECK_ARG(step > 0 || !checkpoint, "the start (step 0) is no checkpoint");
+  MIA_CHECK_ARG(step > 0 || (eta0 > 0.f && __builtin_isfinite(eta0)),
+                "the start (step 0) needs a finite eta0 > 0");
+  // every pair of the six arrays: fstate 4·N floats, istate 3·N ints, the others N words
+  const float* b[6] = {loss, fstate, (const float*)istate, (const float*)action, hist_loss,
+                       hist_eta};
+  const int64_t len[6] = {N, 4LL * N, 3LL * N, N, N, N};
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j)  // b[j] must not start inside b[i]
+      MIA_CHECK_ARG(i == j || b[j] < b[i] ||
+                        (uintptr_t)b[j] - (uintptr_t)b[i] >= (uintptr_t)len[i] * sizeof(float),
+                    "the state, action, loss and history arrays must be distinct buffers");
+  MIA_LAUNCH(apgd_decide_kernel, dim3((N + 63) / 64), dim3(64), 0, loss, fstate, istate, action,
+             hist_loss, hist_eta, N, step, checkpoint, thr, eta0);
+}
+
+extern "C" int mia_apgd_apply(float* x, float* g, float* x_best, float* g_best, const int* action,
+                              int N, int64_t plane, void* stream) {
+  MIA_CHECK_ARG(x && g && x_best && g_best && action, "null argument");
+  MIA_CHECK_IMAGES(N, plane);
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(x, g, len) && !di_overlap(x, x_best, len) &&
+                    !di_overlap(x, g_best, len) && !di_overlap(g, x_best, len) &&
+                    !di_overlap(g, g_best, len) && !di_overlap(x_best, g_best, len),
+                "x, g, x_best and g_best must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(g) && aligned16(x_best) &&
+                   aligned16(g_best);
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  if (vec)
+    MIA_LAUNCH(apgd_apply_kernel<true>, grid, dim3(TPB), 0, x, g, x_best, g_best, action, plane);
+  MIA_LAUNCH(apgd_apply_kernel<false>, grid, dim3(TPB), 0, x, g, x_best, g_best, action, plane);
 }
 
 extern "C" int mia_cw_init(const float* x, float* w, int64_t len, void* stream) {

@@ -69,7 +69,10 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       state on host or device. Every shard is attacked with ``vt_first_image`` = the caller's
       value (default 0, the global index of ``imgs[0]``) + the shard's first row, so each image
       draws the noise it draws in a single-process attack of the full batch, and the output
-      does not depend on the world size."""
+      does not depend on the world size.
+    * Auto-PGD (``apgd=True``) needs nothing more: its step sizes, counters and best iterates
+      are per image and live on the shard's device, and its only random state is the start
+      noise sliced above, so the output does not depend on the world size."""
     from . import pgd
     group = group if group is not None else dist.group.WORLD
     world = dist.get_world_size(group)

@@ -793,6 +793,92 @@ def vt_combine_norms(g, gv, v, gt, l1, nonfinite=None):
     return gt
 
 
+APGD_SAVE, APGD_RESTORE = 1, 2  # MIA_APGD_SAVE, MIA_APGD_RESTORE: the bits of an action word
+
+
+def _distinct(bufs):
+    """bufs: (name, tensor) pairs that must not share a base address."""
+    for i, (na, a) in enumerate(bufs):
+        for nb, b in bufs[i + 1:]:
+            if a.data_ptr() == b.data_ptr():
+                raise ValueError(f"{na} and {nb} must be distinct buffers")
+
+
+def apgd_update(x, x_old, x0, g, eta, a, e, lo=-1.0, hi=1.0, nonfinite=None):
+    """The Auto-PGD momentum step with the per-image step size eta[n] (mia_apgd_update):
+    d = x − x_old; x_old ← x; z = clamp(min(max(x − eta·sign(g), x0 − e), x0 + e), lo, hi);
+    x ← clamp(min(max((x + (z − x)·a) + d·(1 − a), x0 − e), x0 + e), lo, hi).
+    x, x_old, x0, g: distinct fp32 batches of one shape; eta: fp32 [N]; a in (0, 1]."""
+    N, plane = _si_images(x, x_old, "x", "x_old")
+    _need(x0, x.shape, torch.float32, "x0")
+    _need(g, x.shape, torch.float32, "g")
+    _distinct([("x", x), ("x_old", x_old), ("x0", x0), ("g", g)])
+    _need(eta, (N,), torch.float32, "eta")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    if isinstance(a, bool) or not isinstance(a, numbers.Real) or not 0.0 < a <= 1.0:
+        raise ValueError("a must be a number in (0, 1]")
+    if isinstance(e, bool) or not isinstance(e, numbers.Real) or not math.isfinite(e) or e <= 0:
+        raise ValueError("e must be a finite number > 0")
+    if not float(lo) <= float(hi):
+        raise ValueError("need lo <= hi")
+    call("mia_apgd_update", ptr(x), ptr(x_old), ptr(x0), ptr(g), ptr(eta), N, plane, float(a),
+         float(e), float(lo), float(hi), ptr(nonfinite), stream())
+    return x
+
+
+def apgd_decide(loss, fstate, istate, action, hist_loss, hist_eta, step, checkpoint=False, thr=0,
+                eta0=None):
+    """The per-image step-size control of Auto-PGD on loss[n] (mia_apgd_decide). fstate: fp32
+    (4, N) rows eta, L_best, L_prev, L_check; istate: int32 (3, N) rows n_dec, reduced,
+    best_step; action: int32 [N], overwritten with APGD_SAVE / APGD_RESTORE bits; hist_loss,
+    hist_eta: fp32 (rows, N) histories whose row ``step`` receives (loss, eta after the step).
+    step = 0 is the start (needs eta0, no checkpoint); step = i + 1 follows update i, a
+    checkpoint with the integer threshold ``thr``."""
+    if loss is None or loss.dim() != 1 or loss.dtype != torch.float32 or loss.numel() == 0:
+        raise ValueError("loss must be a non-empty 1-D fp32 tensor")
+    N = loss.numel()
+    _need(fstate, (4, N), torch.float32, "fstate")
+    _need(istate, (3, N), torch.int32, "istate")
+    _need(action, (N,), torch.int32, "action")
+    for v, nm in ((step, "step"), (thr, "thr")):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v < 1 << 31:
+            raise ValueError(f"{nm} must be an integer in 0 … 2^31 − 1")
+    step, thr = int(step), int(thr)
+    if not isinstance(checkpoint, (bool, int)) or checkpoint not in (0, 1):
+        raise ValueError("checkpoint must be True or False")
+    for h, nm in ((hist_loss, "hist_loss"), (hist_eta, "hist_eta")):
+        if h is None or h.dim() != 2 or h.dtype != torch.float32 or h.shape[1] != N:
+            raise ValueError(f"{nm} must be an fp32 (rows, N) tensor")
+        if not step < h.shape[0]:
+            raise ValueError(f"{nm} has no row {step}")
+    _distinct([("loss", loss), ("fstate", fstate), ("hist_loss", hist_loss),
+               ("hist_eta", hist_eta)])
+    if step == 0:
+        if checkpoint:
+            raise ValueError("the start (step 0) is no checkpoint")
+        if (isinstance(eta0, bool) or not isinstance(eta0, numbers.Real)
+                or not math.isfinite(eta0) or eta0 <= 0):
+            raise ValueError("the start (step 0) needs a finite eta0 > 0")
+    call("mia_apgd_decide", ptr(loss), ptr(fstate), ptr(istate), ptr(action), ptr(hist_loss[step]),
+         ptr(hist_eta[step]), N, step, int(checkpoint), thr, float(eta0) if step == 0 else 0.0,
+         stream())
+    return action
+
+
+def apgd_apply(x, g, x_best, g_best, action):
+    """The whole-image copies an action word asks for (mia_apgd_apply): APGD_SAVE: x_best ← x,
+    g_best ← g; otherwise APGD_RESTORE: x ← x_best, g ← g_best; 0: the image is not touched.
+    x, g, x_best, g_best: distinct fp32 batches of one shape; action: int32 [N]."""
+    N, plane = _si_images(x, g, "x", "g")
+    _need(x_best, x.shape, torch.float32, "x_best")
+    _need(g_best, x.shape, torch.float32, "g_best")
+    _distinct([("x", x), ("g", g), ("x_best", x_best), ("g_best", g_best)])
+    _need(action, (N,), torch.int32, "action")
+    call("mia_apgd_apply", ptr(x), ptr(g), ptr(x_best), ptr(g_best), ptr(action), N, plane,
+         stream())
+    return x
+
+
 def cw_init(x, w):
     _need(w, x.shape, torch.float32, "w")
     call("mia_cw_init", ptr(x), ptr(w), x.numel(), stream())

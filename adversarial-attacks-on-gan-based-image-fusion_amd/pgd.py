@@ -636,6 +636,130 @@ class AttackEngine:
                          si_scales, step_vt)
         return x.clone()
 
+    # ---- Auto-PGD ------------------------------------------------------------------------------
+    def _apgd_buffers(self, shape, steps=None):
+        """The workspace buffers ``apgd.*`` of a batch of ``shape`` (``steps``: of the attack that
+        start_apgd began): images x_old, x_best, g_best; the per-image state ``state_f`` (fp32
+        rows eta, L_best, L_prev, L_check) and ``state_i`` (int32 rows n_dec, reduced, best_step);
+        the action words; the step's objective ``f``; the histories ``loss`` / ``step_size``
+        (steps + 1, N)."""
+        ws, f32, i32, N = self.ws, torch.float32, torch.int32, shape[0]
+        steps = self.apgd_steps if steps is None else steps
+        b = {k: ws.get("apgd." + k, shape, f32) for k in ("x_old", "x_best", "g_best")}
+        b.update(state_f=ws.get("apgd.state_f", (4, N), f32),
+                 state_i=ws.get("apgd.state_i", (3, N), i32),
+                 action=ws.get("apgd.action", (N,), i32), f=ws.get("apgd.f", (N,), f32),
+                 loss=ws.get("apgd.loss", (steps + 1, N), f32),
+                 step_size=ws.get("apgd.step_size", (steps + 1, N), f32),
+                 g=ws.get("g.full", shape, f32))
+        return b
+
+    def start_apgd(self, x0, t, steps, eps, random_start=False, start_noise=None):
+        """prepare(), the iterate at x0 (or the L∞ random start) and the Auto-PGD state of a
+        ``steps``-step attack: one gradient pass at the start gives g and L(x), then x_old =
+        x_best = x, g_best = g, L_best = L_prev = L_check = L(x), eta = 2·e, n_dec = 0,
+        reduced = 1 and row 0 of the histories (ops.apgd_decide at step 0, ops.apgd_apply).
+        Returns the iterate buffer for step_apgd."""
+        self.apgd_steps = int(steps)
+        self.apgd_e = e = _f32(2.0 * eps)
+        self.apgd_rows = {i: (k, thr) for i, k, thr in apgd_schedule(steps)}
+        x = self._start(x0, t, e, random_start, start_noise)
+        b = self._apgd_buffers(x0.shape)
+        ops.zero_(b["f"])
+        self._full_grad(x, b["g"], loss=b["f"])
+        b["x_old"].copy_(x)
+        ops.apgd_decide(b["f"], b["state_f"], b["state_i"], b["action"], b["loss"],
+                        b["step_size"], 0, eta0=_f32(2.0 * e))
+        ops.apgd_apply(x, b["g"], b["x_best"], b["g_best"], b["action"])
+        return x
+
+    def step_apgd(self, x, i):
+        """Step i (0-based) of the attack start_apgd began, on the iterate x in place: the
+        momentum update with the per-image step size (ops.apgd_update; weight 1 at i = 0,
+        APGD_MOMENTUM after), one gradient pass for g and L_i at the new x, the per-image control
+        (ops.apgd_decide, a checkpoint where apgd_schedule has a row for i) and the copies it
+        asks for (ops.apgd_apply: keep the best x and g, or restart from them). Nothing is read
+        back to the host."""
+        if not 0 <= i < self.apgd_steps:
+            raise ValueError("step index outside the attack start_apgd began")
+        b = self._apgd_buffers(x.shape)
+        ops.apgd_update(x, b["x_old"], self.x0, b["g"], b["state_f"][0],
+                        1.0 if i == 0 else _f32(APGD_MOMENTUM), self.apgd_e,
+                        nonfinite=self.nonfinite)
+        ops.zero_(b["f"])
+        self._full_grad(x, b["g"], loss=b["f"])
+        k, thr = self.apgd_rows.get(i, (0, 0))
+        ops.apgd_decide(b["f"], b["state_f"], b["state_i"], b["action"], b["loss"],
+                        b["step_size"], i + 1, checkpoint=k > 0, thr=thr)
+        ops.apgd_apply(x, b["g"], b["x_best"], b["g_best"], b["action"])
+        return x
+
+    def run_apgd(self, x0, t, steps, eps, random_start=False, start_noise=None, group=None):
+        """Auto-PGD, L∞ (Croce & Hein 2020; torchattacks APGD.attack_single_run with
+        norm='Linf', eot_iter=1, one run) descending L, with e = 2·eps; no alpha. Per image n a
+        step size eta[n] starts at 2·e; step i (a = 1 for i = 0, else 0.75) is
+            d = x − x_old;  x_old ← x
+            z = clamp(min(max(x − eta[n]·sign(g), x0 − e), x0 + e), −1, 1)
+            x ← clamp(min(max((x + (z − x)·a) + d·(1 − a), x0 − e), x0 + e), −1, 1)
+        followed by the gradient and the objective L_i at the new x in one pass, and per image
+            L_i < L_prev: n_dec += 1;  L_prev = L_i;  L_i < L_best: L_best = L_i, x_best ← x, g_best ← g
+            at a checkpoint (k, thr) of apgd_schedule(steps):
+                flag = n_dec <= thr or (reduced == 0 and L_check <= L_best)
+                reduced = flag;  L_check = L_best;  n_dec = 0;  flag: eta /= 2, x ← x_best, g ← g_best
+        Returns x_best (steps + 1 gradient passes). All state lives on the device (workspace
+        buffers ``apgd.*``): no per-step host synchronisation. An fp16 loss-scale re-run restarts
+        every piece of it.
+
+        One deviation from torchattacks: at the first checkpoint its check_oscillation compares
+        step 0 with loss_steps[-1], a zero row reached by negative indexing; here step 0 is
+        compared with the objective at the starting point, the paper's condition."""
+        return self._with_rescale(
+            lambda: self._run_apgd(x0, t, steps, eps, random_start, start_noise), group)
+
+    def _run_apgd(self, x0, t, steps, eps, random_start, start_noise):
+        x = self.start_apgd(x0, t, steps, eps, random_start, start_noise)
+        for i in range(steps):
+            self.step_apgd(x, i)
+        return self._apgd_buffers(x0.shape)["x_best"].clone()
+
+    def apgd_info(self):
+        """The record of the last Auto-PGD run, on the host (one sync): ``loss`` and ``step_size``
+        (steps + 1, N) — L and eta at the start (row 0) and after step i (row i + 1) —
+        ``best_step`` [N] (0: the start, i + 1: step i) and ``halvings`` [N], how often each
+        image's step size was halved."""
+        b = self._apgd_buffers(self.x0.shape)
+        eta = b["step_size"].cpu()
+        return dict(loss=b["loss"].cpu(), step_size=eta,
+                    best_step=b["state_i"][2].cpu().to(torch.int64),
+                    halvings=(eta[1:] < eta[:-1]).sum(dim=0))
+
+
+APGD_RHO = 0.75       # a checkpoint flags an image with at most floor(ρ·k) decreases in k steps
+APGD_MOMENTUM = 0.75  # the weight a of the new step against the previous displacement (i > 0)
+
+
+def apgd_schedule(steps):
+    """The checkpoints of an Auto-PGD run of ``steps`` steps (torchattacks APGD), a pure function
+    of ``steps``: a list of rows (step index, k, thr). With k0 = max(int(0.22·steps), 1),
+    k_min = max(int(0.06·steps), 1), dec = max(int(0.03·steps), 1): a counter starts at 0 and the
+    window at k = k0; after every step the counter goes up by one; when it equals k, that step is
+    a checkpoint with window k and threshold thr = floor(ρ·k), ρ = APGD_RHO (= 3k // 4, exact);
+    then the counter restarts and k ← max(k − dec, k_min)."""
+    if isinstance(steps, bool) or int(steps) != steps or steps < 0:
+        raise ValueError("need integer steps >= 0")
+    steps = int(steps)
+    k = max(int(0.22 * steps), 1)
+    k_min = max(int(0.06 * steps), 1)
+    dec = max(int(0.03 * steps), 1)
+    rows, counter = [], 0
+    for i in range(steps):
+        counter += 1
+        if counter == k:
+            rows.append((i, k, 3 * k // 4))
+            counter = 0
+            k = max(k - dec, k_min)
+    return rows
+
 
 def _check_images(imgs, size, name):
     if not torch.is_tensor(imgs) or imgs.dim() != 4 or imgs.shape[1] != 3:
@@ -840,7 +964,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
            di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
-           vt_samples=None, vt_beta=1.5, vt_first_image=0):
+           vt_samples=None, vt_beta=1.5, vt_first_image=0, apgd=False):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -942,12 +1066,51 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     vt_first_image  the global index of imgs[0] (default 0), an integer ≥ 0: image n draws the
             noise of image vt_first_image + n, so attacking a slice of a batch with its offset
             gives the rows of the whole batch (``dist.attack_distributed`` passes the shard's).
+    apgd    False (default). True, with norm='linf' only (the L2 form is not implemented):
+            Auto-PGD (Croce & Hein 2020; torchattacks APGD with norm='Linf', eot_iter=1, one
+            run) on the objective, AttackEngine.run_apgd. ``alpha`` is not used: every image has
+            a step size of its own, eta = 2·e at the start, with momentum on the iterate
+            (a = 1 at the first step, 0.75 after):
+                      z = clamp(min(max(x − eta·sign(∇L), x0 − e), x0 + e), −1, 1)
+                      x ← clamp(min(max(x + a·(z − x) + (1 − a)·(x − x_old), x0 − e), x0 + e), −1, 1)
+            The per-image objective comes out of the same pass as the gradient. At the
+            checkpoints of ``apgd_schedule(steps)`` (windows of k steps, k shrinking from
+            0.22·steps to 0.06·steps) an image whose objective fell in at most floor(0.75·k) of
+            the window's steps, or that found no new best since a checkpoint that did not
+            halve, halves its eta and restarts from its best iterate and that iterate's
+            gradient. The result is the BEST iterate of every image (the start included), not
+            the last; steps + 1 gradient passes. Step sizes, counters, best points and the
+            conditional copies all live on the device (fused HIP kernels): no per-step host
+            synchronisation; an fp16 loss-scale re-run restarts all of it. One deviation from
+            torchattacks: at the first checkpoint its check_oscillation compares step 0 with
+            loss_steps[-1], a zero row reached by negative indexing; here step 0 is compared
+            with the objective at the starting point, the paper's condition. It does not
+            combine with momentum, nesterov, ti_kernel, di_prob / di_schedule, si_scales or
+            vt_samples. With return_info, info["apgd"] holds ``loss`` and ``step_size``
+            (steps + 1, N: the start, then after every step), ``best_step`` (0 = the start,
+            i + 1 = step i) and ``halvings`` per image, as host tensors.
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
     Returns the adversarial images on the input's device (fp32), and a dict if return_info.
     """
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}")
+    if not isinstance(apgd, (bool, np.bool_)):
+        raise ValueError("apgd must be True or False")
+    apgd = bool(apgd)
+    if apgd:
+        if norm == "l2":
+            raise ValueError("apgd (Auto-PGD): the L2 form is not implemented, use norm='linf'")
+        if norm != "linf":
+            raise ValueError("apgd (Auto-PGD) is implemented for norm='linf' only")
+        mixed = [name for name, on in (
+            ("momentum", momentum is not None), ("nesterov", not isinstance(nesterov, (bool, np.bool_)) or bool(nesterov)),
+            ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
+            ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
+            ("vt_samples", vt_samples is not None)) if on]
+        if mixed:
+            raise ValueError(f"apgd (Auto-PGD) does not combine with {', '.join(mixed)}: it has "
+                             "its own momentum and step-size rule")
     if momentum is not None:
         if norm != "linf":
             raise ValueError("momentum (MI-FGSM) is implemented for norm='linf' only")
@@ -1030,8 +1193,10 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
-                           or n_si > 1 or n_vt is not None):
+    if apgd:
+        adv = eng.run_apgd(x0, t, int(steps), float(eps), random_start, noise, group=group)
+    elif norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
+                             or n_si > 1 or n_vt is not None):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
                          float(momentum) if momentum is not None else 0.0, random_start, noise,
                          group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si,
@@ -1057,6 +1222,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     di_applied=int(di[:, 3].sum()) if di is not None else 0,
                     si_scales=si_scales, nesterov=nesterov, vt_samples=vt_samples,
                     vt_beta=vt_beta if vt_samples is not None else None)
+        if apgd:
+            info["apgd"] = eng.apgd_info()
         return adv, info
     return adv
 
@@ -1064,7 +1231,11 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
 def fgsm(net, imgs, eps, **kw):
     """FGSM = one PGD step with α = ε and no random start. Every other keyword is forwarded
     unchanged (nesterov's look-ahead is a no-op at the only step, where the momentum is 0; so is
-    vt_samples, whose variance term is 0 there: plain FGSM)."""
+    vt_samples, whose variance term is 0 there: plain FGSM). ``apgd=True`` is rejected: one step
+    of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM."""
+    if kw.get("apgd"):
+        raise ValueError("fgsm() takes no apgd: one step of Auto-PGD is not FGSM; call "
+                         "attack(..., steps=1, apgd=True) for that")
     kw.pop("alpha", None)
     kw.pop("random_start", None)
     return attack(net, imgs, eps, 1, alpha=eps, random_start=False, **kw)

@@ -528,6 +528,59 @@ int mia_vt_neighbor(const float* x, const float* m, float* y, int N, int64_t pla
  * (NULL or int[N]) is set for an image with a non-finite element of gt or of the new v. */
 int mia_vt_combine_norms(const float* g, const float* gv, float* v, float* gt, float* l1, int N,
                          int64_t plane, int* nonfinite, void* stream);
+/* Auto-PGD (Croce & Hein 2020; torchattacks APGD.attack_single_run, norm = 'Linf', eot_iter = 1)
+ * on cost = −L, images in [-1,1]: three launches per step, all decisions on the device. Per-image
+ * state is written by mia_apgd_decide alone (one thread per image) and only read by the other
+ * two, whose many blocks per image therefore never read what a block of the same launch writes.
+ *
+ * The momentum step with a per-image step size, per element of image n:
+ *   d = x − x_old;  x_old = x
+ *   z = clamp(min(max(x − eta[n]·sign(g), x0 − e), x0 + e), lo, hi)
+ *   x = clamp(min(max((x + (z − x)·a) + d·(1 − a), x0 − e), x0 + e), lo, hi)   (in place)
+ * — torchattacks' bound form (x0 − e and x0 + e are one rounding each), not the delta form of
+ * mia_mi_update / mia_pgd_update. One fp32 rounding per operation, no contraction, 1 − a computed
+ * in fp32 in the kernel: bit-exact vs torch fp32 ops. sign(0) = 0; g may carry any positive scale.
+ * x, x_old, x0, g: fp32, N images of `plane` elements, distinct buffers; eta: fp32 [N] in device
+ * memory; a in (0, 1] (1 on the first step, 0.75 after); e finite and > 0; lo ≤ hi; N in
+ * 1 … 65535, plane < 2^31 (anything else: MIA_EINVAL before any launch). nonfinite (NULL or
+ * int[N]) is set for an image with a non-finite element of g (whose sign counts as 0). A thread
+ * owns 4 consecutive elements of one image whether it moves them as one 16-byte vector
+ * (plane % 4 == 0, 16-byte aligned buffers) or as scalars: the same bits; an image's result does
+ * not depend on the other images of the call. */
+int mia_apgd_update(float* x, float* x_old, const float* x0, const float* g, const float* eta,
+                    int N, int64_t plane, float a, float e, float lo, float hi, int* nonfinite,
+                    void* stream);
+/* The step-size control of Auto-PGD, one thread per image n, on L = loss[n] (the objective at
+ * the iterate the last update produced). State: fstate fp32 (4, N) rows eta, L_best, L_prev,
+ * L_check; istate int32 (3, N) rows n_dec, reduced, best_step.
+ *   step = 0 (the start): eta = eta0; L_best = L_prev = L_check = L; n_dec = 0; reduced = 1;
+ *                         best_step = 0; action = MIA_APGD_SAVE.
+ *   step = i + 1 (after update i):
+ *     L < L_prev: n_dec += 1;   L_prev = L
+ *     L < L_best: L_best = L; best_step = step; action |= MIA_APGD_SAVE
+ *     checkpoint ≠ 0: flag = n_dec <= thr || (reduced == 0 && L_check <= L_best)
+ *                     reduced = flag; L_check = L_best; n_dec = 0
+ *                     flag: eta = eta / 2; action |= MIA_APGD_RESTORE
+ * (thr = floor(0.75·k) for a window of k steps). A NaN objective fails every comparison: it is
+ * never a decrease and never the best. action[n] (int32) is overwritten; hist_loss[n] = L and
+ * hist_eta[n] = eta after the step (the caller passes row `step` of its (steps + 1, N)
+ * histories). Every array in device memory, all distinct; N in 1 … 65535, step ≥ 0, checkpoint in
+ * {0, 1} (0 at the start), thr ≥ 0, eta0 finite and > 0 at the start (anything else: MIA_EINVAL
+ * before any launch). */
+#define MIA_APGD_SAVE 1
+#define MIA_APGD_RESTORE 2
+int mia_apgd_decide(const float* loss, float* fstate, int* istate, int* action, float* hist_loss,
+                    float* hist_eta, int N, int step, int checkpoint, int thr, float eta0,
+                    void* stream);
+/* The whole-image copies mia_apgd_decide asked for, per image n (action from an EARLIER launch):
+ *   action[n] & MIA_APGD_SAVE:  x_best = x, g_best = g    (keep the best iterate and its gradient)
+ *   else & MIA_APGD_RESTORE:    x = x_best, g = g_best    (restart from the best point)
+ *   else: image n is not touched.
+ * With both bits the best point is the iterate itself, the restore is the identity and only the
+ * save runs. x, g, x_best, g_best: fp32, N images of `plane` elements, distinct buffers; bit
+ * copies, vector or scalar as above. */
+int mia_apgd_apply(float* x, float* g, float* x_best, float* g_best, const int* action, int N,
+                   int64_t plane, void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);
