@@ -1293,8 +1293,16 @@ def se_apply(r, s, sc, ss, out, g=None, b=None, xb=None):
     return out if out is not None else xb
 
 
+def _chan_vec_ok(C, name):
+    # the rule of mia_chan_dot / mia_chan_sum (csrc/encoder.hip: ENC_CHECK_C and C ≤ 2048), checked
+    # here so that a bad channel count is a ValueError like the other shape errors; keep in step
+    if C <= 0 or C % 8 or C > 2048:
+        raise ValueError(f"{name}: C = {C} must be a multiple of 8, at most 2048")
+
+
 def chan_dot(a, b, gs, accumulate=False):
     N, H, W, C = a.shape
+    _chan_vec_ok(C, "chan_dot")
     _need(b, a.shape, a.dtype, "b")
     _need(gs, (N, C), torch.float32, "gs")
     call("mia_chan_dot", ptr(a), ptr(b), ptr(gs), N, H * W, C, int(bool(accumulate)), dt(a),
@@ -1312,6 +1320,7 @@ def chan_sum(a, b, part, out, accumulate=False):
     part: fp32 scratch of N · chan_sum_parts(N, H·W) · C floats. out None: only the ordered
     per-chunk partials (for se_fwd_parts / se_bwd_parts); returns part then."""
     N, H, W, C = a.shape
+    _chan_vec_ok(C, "chan_sum")
     if b is not None:
         _need(b, a.shape, a.dtype, "b")
     if out is not None:

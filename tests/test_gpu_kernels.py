@@ -589,7 +589,9 @@ def test_gemm_and_demod(cuda):
 @pytest.mark.parametrize("M,n_groups", [(7, 3), (128, 14), (300, 20)])
 def test_gemm_grouped_two_segments(cuda, M, n_groups):
     """Grouped GEMM: per group C = α(A1·B1 + A2·B2) + βC + bias with strided views; > 12 groups
-    exercises the launch split, M = 300 the 64-tile path, M = 7 the 32-tile path."""
+    exercises the launch split. Every case runs the 32-tile kernel: the largest, M = 300 with 20
+    groups, has 5·Σ⌈N/64⌉ = 5·41 = 205 64-tiles, below the 512 at which the host picks the 64-tile
+    kernel (that one is run by tests/test_gpu_linalg_ref.py)."""
     g = torch.Generator().manual_seed(M)
     plan = ops.GemmPlan()
     want, outs = [], []
