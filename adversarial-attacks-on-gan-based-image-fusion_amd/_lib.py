@@ -152,6 +152,11 @@ SIGNATURES = {
     "mia_vt_neighbor": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, ctypes.c_uint64,
                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]),
     "mia_vt_combine_norms": (c_int, [P, P, P, P, P, c_int, c_int64, P, P]),
+    "mia_spsa_probe": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, c_float, ctypes.c_uint64,
+                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]),
+    "mia_spsa_accumulate_norms": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, ctypes.c_uint64,
+                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int,
+                                          c_float, P, P]),
     "mia_apgd_update": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float,
                                 P, P]),
     "mia_apgd_decide": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),

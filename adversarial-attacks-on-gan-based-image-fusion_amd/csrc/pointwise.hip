@@ -1340,6 +1340,97 @@ __global__ __launch_bounds__(TPB) void vt_combine_norms_kernel(
   block_slot_store<1>(lane_sum<4>(a1), 0.f, part);
 }
 
+// ---- SPSA (Spall 1992; Uesato et al. 2018; torchattacks SPSA's estimator), a score-based
+// black-box attack: the gradient is estimated from objective VALUES at antithetic probes
+// x ± d·v, v Rademacher. Both kernels run on the VT kernels' (slots, N) grid, a thread owning one
+// group of 4 consecutive elements of its image = one Philox block, counter (group index, GLOBAL
+// image index, step, sample): the directions are never stored, the accumulation regenerates them.
+// v = +1 where bit 31 of the element's word is 0, −1 where it is 1.
+//
+// The two probes of one pair in one pass (one read of x, one Philox block):
+//   t = v > 0 ? d : −d;  yp = clamp(x + t, lo, hi);  ym = clamp(x − t, lo, hi)
+// One fp32 rounding per operation.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void spsa_probe_kernel(const float* __restrict__ x,
+                                                         float* __restrict__ yp,
+                                                         float* __restrict__ ym, int64_t plane,
+                                                         float d, float lo, float hi, uint32_t k0,
+                                                         uint32_t k1, uint32_t image0,
+                                                         uint32_t step, uint32_t sample) {
+#pragma clang fp contract(off)
+  const int64_t base = (int64_t)blockIdx.y * plane, ng = (plane + 3) / 4;
+  const uint32_t image = image0 + blockIdx.y;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    float v[4], p[4], q[4];
+    ld4<VEC>(x + i0, cnt, v);
+    uint32_t b[4];
+    philox4x32_10((uint32_t)j, image, step, sample, k0, k1, b);  // j < 2^29
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float t = (b[e] >> 31) ? -d : d;
+      const float up = v[e] + t;
+      const float dn = v[e] - t;
+      p[e] = fminf(fmaxf(up, lo), hi);
+      q[e] = fminf(fmaxf(dn, lo), hi);
+    }
+    st4<VEC>(yp + i0, cnt, p);
+    st4<VEC>(ym + i0, cnt, q);
+  }
+}
+
+// One pair's term into the step's estimate, with the per-image norms of the result:
+//   c = (fp[n] − fm[n])·s;  t = v > 0 ? c : −c;  r = first ? t : acc + t;
+//   div ≠ 1: r = r / div (IEEE);  acc = r
+// with the per-image partial sums of |r| (quantity 0) and r² (quantity 1), as
+// si_accumulate_norms_kernel. One fp32 rounding per operation; r² enters its sum through an fma,
+// unrounded. A non-finite objective reaches every r of its image through c.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void spsa_accumulate_norms_kernel(
+    float* __restrict__ acc, const float* __restrict__ fp, const float* __restrict__ fm,
+    float* __restrict__ part, int64_t plane, float s, uint32_t k0, uint32_t k1, uint32_t image0,
+    uint32_t step, uint32_t sample, int first, float div, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const int64_t base = (int64_t)n * plane, ng = (plane + 3) / 4;
+  const uint32_t image = image0 + blockIdx.y;
+  const float df = fp[n] - fm[n];
+  const float c = df * s;
+  float a1[4], a2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a1[e] = a2[e] = 0.f;
+  bool bad = false;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = base + j * 4;
+    const int cnt = (int)(plane - j * 4 < 4 ? plane - j * 4 : 4);
+    uint32_t b[4];
+    philox4x32_10((uint32_t)j, image, step, sample, k0, k1, b);  // j < 2^29
+    float r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = e < cnt ? ((b[e] >> 31) ? -c : c) : 0.f;
+    if (!first) {
+      float av[4];
+      ld4<VEC>(acc + i0, cnt, av);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = av[e] + r[e];
+    }
+    if (div != 1.f) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = r[e] / div;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {  // the lanes past a partial group hold 0
+      bad |= !__builtin_isfinite(r[e]);
+      a1[e] += fabsf(r[e]);
+      a2[e] = fmaf(r[e], r[e], a2[e]);
+    }
+    st4<VEC>(acc + i0, cnt, r);
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+  block_slot_store<2>(lane_sum<4>(a1), lane_sum<4>(a2), part);
+}
+
 // ---- Auto-PGD (Croce & Hein 2020; torchattacks APGD.attack_single_run, norm = 'Linf') on
 // cost = −L. Three kernels per step. The update and the copies run on the SI kernels' (slots, N)
 // grid, a thread owning one group of 4 consecutive elements of its image, so VEC and the guarded
@@ -2644,6 +2735,61 @@ extern "C" int mia_vt_combine_norms(const float* g, const float* gv, float* v, f
     hipLaunchKernelGGL(vt_combine_norms_kernel<false>, grid, dim3(TPB), 0, st, g, gv, v, gt,
                        r.part, plane, nonfinite);
   rc = check_launch("vt_combine_norms_kernel");
+  return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+extern "C" int mia_spsa_probe(const float* x, float* yp, float* ym, int N, int64_t plane, float d,
+                              float lo, float hi, uint64_t seed, uint32_t image0, uint32_t step,
+                              uint32_t sample, void* stream) {
+  MIA_CHECK_ARG(x && yp && ym, "null x / yp / ym");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG((uint64_t)image0 + (uint64_t)N <= (1ULL << 32), "image0 + N must be <= 2^32");
+  MIA_CHECK_ARG(__builtin_isfinite(d) && d > 0.f, "d must be finite and > 0");
+  MIA_CHECK_ARG(lo <= hi, "need lo <= hi");
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(x, yp, len) && !di_overlap(x, ym, len) && !di_overlap(yp, ym, len),
+                "x, yp and ym must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(yp) && aligned16(ym);
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+  if (vec)
+    MIA_LAUNCH(spsa_probe_kernel<true>, grid, dim3(TPB), 0, x, yp, ym, plane, d, lo, hi, k0, k1,
+               image0, step, sample);
+  MIA_LAUNCH(spsa_probe_kernel<false>, grid, dim3(TPB), 0, x, yp, ym, plane, d, lo, hi, k0, k1,
+             image0, step, sample);
+}
+
+extern "C" int mia_spsa_accumulate_norms(float* acc, const float* fp, const float* fm, float* l1,
+                                         float* l2sq, int N, int64_t plane, float s, uint64_t seed,
+                                         uint32_t image0, uint32_t step, uint32_t sample, int first,
+                                         float div, int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(acc && fp && fm, "null acc / fp / fm");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG((uint64_t)image0 + (uint64_t)N <= (1ULL << 32), "image0 + N must be <= 2^32");
+  MIA_CHECK_ARG(__builtin_isfinite(s) && s > 0.f, "s must be finite and > 0");
+  MIA_CHECK_ARG(__builtin_isfinite(div) && div > 0.f, "div must be finite and > 0");
+  // acc: N·plane floats; fp, fm: N floats each
+  const auto inside = [](const float* a, int64_t la, const float* b, int64_t lb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb ? pb - pa < (uintptr_t)la * sizeof(float) : pa - pb < (uintptr_t)lb * sizeof(float);
+  };
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!inside(acc, len, fp, N) && !inside(acc, len, fm, N) && !inside(fp, N, fm, N),
+                "acc, fp and fm must be distinct buffers");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool vec = plane % 4 == 0 && aligned16(acc);
+  const dim3 grid = image_grid(plane + 3, 4, N);
+  const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+  RedQ r;
+  int rc = red_begin(r, l1, l2sq, nullptr, grid.x, N, st);
+  if (rc != MIA_OK) return rc;
+  if (vec)
+    hipLaunchKernelGGL(spsa_accumulate_norms_kernel<true>, grid, dim3(TPB), 0, st, acc, fp, fm,
+                       r.part, plane, s, k0, k1, image0, step, sample, first != 0, div, nonfinite);
+  else
+    hipLaunchKernelGGL(spsa_accumulate_norms_kernel<false>, grid, dim3(TPB), 0, st, acc, fp, fm,
+                       r.part, plane, s, k0, k1, image0, step, sample, first != 0, div, nonfinite);
+  rc = check_launch("spsa_accumulate_norms_kernel");
   return rc != MIA_OK ? rc : red_finish(r, st);
 }
 

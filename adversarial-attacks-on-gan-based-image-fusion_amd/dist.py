@@ -70,6 +70,11 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       value (default 0, the global index of ``imgs[0]``) + the shard's first row, so each image
       draws the noise it draws in a single-process attack of the full batch, and the output
       does not depend on the world size.
+    * SPSA (``spsa_samples``, ``spsa_delta``): the black-box attack's random directions are the
+      same kind of pure function of (seed, global image index, step, pair, element index). Every
+      shard is attacked with ``spsa_first_image`` = the caller's value (default 0) + the shard's
+      first row, so each image probes along the directions it takes in a single-process attack
+      of the full batch, and the output does not depend on the world size.
     * Auto-PGD (``apgd=True``) needs nothing more: its step sizes, counters and best iterates
       are per image and live on the shard's device, and its only random state is the start
       noise sliced above, so the output does not depend on the world size."""
@@ -93,6 +98,10 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
         first = kw.get("vt_first_image", 0)
         if isinstance(first, numbers.Integral) and not isinstance(first, bool):
             kw = dict(kw, vt_first_image=int(first) + lo)  # anything else: attack() rejects it
+    if "spsa_samples" in kw or "spsa_first_image" in kw:
+        first = kw.get("spsa_first_image", 0)
+        if isinstance(first, numbers.Integral) and not isinstance(first, bool):
+            kw = dict(kw, spsa_first_image=int(first) + lo)
     local = pgd.attack(net, imgs[lo:hi], eps, steps, target=tgt, random_start=random_start,
                        seed=seed, start_noise=noise, group=group, **kw)
     return gather_shards(local.to(gather_dev, torch.float32), n, group).to(imgs.device)

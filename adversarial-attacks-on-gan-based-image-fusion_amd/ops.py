@@ -793,6 +793,64 @@ def vt_combine_norms(g, gv, v, gt, l1, nonfinite=None):
     return gt
 
 
+def _spsa_counter(N, seed, image0, step, sample):
+    """The key and counter words of the SPSA directions, checked as vt_neighbor checks its own."""
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be an integer in 0 … 2^64 − 1")
+    image0, step, sample = (_vt_u32(v, nm) for v, nm in ((image0, "image0"), (step, "step"),
+                                                         (sample, "sample")))
+    if image0 + N > 1 << 32:
+        raise ValueError("image0 + N must be <= 2^32")
+    return int(seed), image0, step, sample
+
+
+def _positive(v, name):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f"{name} must be a finite number > 0")
+    return float(v)
+
+
+def spsa_probe(x, yp, ym, d, seed, image0, step, sample, lo=-1.0, hi=1.0):
+    """yp ← clamp(x + d·v, lo, hi), ym ← clamp(x − d·v, lo, hi): the two probes of one antithetic
+    SPSA pair in one pass, v = ±1 (Rademacher) from bit 31 of the Philox4x32-10 word with the key
+    ``seed`` (0 … 2^64 − 1) and the counter (element index / 4, image0 + n, step, sample)
+    (mia_spsa_probe). Stateless, as vt_neighbor. x, yp, ym: three distinct fp32 batches of one
+    shape; d finite and > 0; lo <= hi."""
+    N, plane = _si_images(x, yp, "x", "yp")
+    _need(ym, x.shape, torch.float32, "ym")
+    _distinct([("x", x), ("yp", yp), ("ym", ym)])
+    d = _positive(d, "d")
+    if not float(lo) <= float(hi):
+        raise ValueError("need lo <= hi")
+    seed, image0, step, sample = _spsa_counter(N, seed, image0, step, sample)
+    call("mia_spsa_probe", ptr(x), ptr(yp), ptr(ym), N, plane, d, float(lo), float(hi), seed,
+         image0, step, sample, stream())
+    return yp, ym
+
+
+def spsa_accumulate_norms(acc, fp, fm, l1, l2sq, s, seed, image0, step, sample, first, div=1.0,
+                          nonfinite=None):
+    """acc ← (first ? c·v : acc + c·v) / div with c = (fp[n] − fm[n])·s and the direction v of
+    spsa_probe regenerated from the same counter (div = 1: no division), with l1[n] += Σ|acc_n|
+    and l2sq[n] += Σ acc_n² (either may be None) (mia_spsa_accumulate_norms). acc: an fp32 batch;
+    fp, fm: distinct fp32 (N,) device tensors, the objective at the two probes; s and div finite
+    and > 0."""
+    if acc is None or acc.dim() < 2 or acc.dtype != torch.float32 or acc.numel() == 0:
+        raise ValueError("acc must be a non-empty fp32 batch of images")
+    N, plane = acc.shape[0], acc.numel() // acc.shape[0]
+    _need(fp, (N,), torch.float32, "fp")
+    _need(fm, (N,), torch.float32, "fm")
+    _distinct([("acc", acc), ("fp", fp), ("fm", fm)])
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    s, div = _positive(s, "s"), _positive(div, "div")
+    seed, image0, step, sample = _spsa_counter(N, seed, image0, step, sample)
+    call("mia_spsa_accumulate_norms", ptr(acc), ptr(fp), ptr(fm), ptr(l1), ptr(l2sq), N, plane, s,
+         seed, image0, step, sample, 1 if first else 0, div, ptr(nonfinite), stream())
+    return acc
+
+
 APGD_SAVE, APGD_RESTORE = 1, 2  # MIA_APGD_SAVE, MIA_APGD_RESTORE: the bits of an action word
 
 

@@ -636,6 +636,90 @@ class AttackEngine:
                          si_scales, step_vt)
         return x.clone()
 
+    # ---- SPSA: the score-based black-box attack ------------------------------------------------
+    def spsa_gradient(self, x, sp, l1=None, l2sq=None):
+        """The SPSA estimate of ∇_x L at x (Spall 1992; Uesato et al. 2018; torchattacks SPSA's
+        estimator) from objective VALUES only, ``sp`` a SpsaStep (samples = q, d, seed, image0,
+        step):
+            per pair i = 0 … q − 1:  x⁺ = clamp(x + d·v_i, −1, 1), x⁻ = clamp(x − d·v_i, −1, 1)
+                                     f⁺ = L(x⁺), f⁻ = L(x⁻)             (objective(): forward only)
+                                     ĝ ← ĝ + (f⁺ − f⁻)·s·v_i,  s = fp32(1/(2·d));  / q on the last
+        v_i is the Rademacher direction of (seed, image0 + n, step, i, element): ops.spsa_probe
+        writes both probes in one pass (buffers spsa.xp, spsa.xm) and ops.spsa_accumulate_norms
+        regenerates v_i from the same counter, so no direction is ever stored. f⁺ and f⁻ stay on
+        the device (spsa.fp, spsa.fm): no host synchronisation. The last accumulation takes the
+        per-image Σ|ĝ| (l1) / Σĝ² (l2sq; either may be None) and a non-finite objective marks
+        its image in self.nonfinite. 2·q forward passes and no backward pass; the loss scale
+        plays no part. Returns ĝ (spsa.g; the next call overwrites it)."""
+        ws, f32 = self.ws, torch.float32
+        N, q = x.shape[0], int(sp.samples)
+        if not 1 <= q <= SPSA_MAX_SAMPLES:
+            raise ValueError(f"spsa samples must be an integer in 1 … {SPSA_MAX_SAMPLES}")
+        xp, xm = ws.get("spsa.xp", x.shape, f32), ws.get("spsa.xm", x.shape, f32)
+        fp, fm = ws.get("spsa.fp", (N,), f32), ws.get("spsa.fm", (N,), f32)
+        g = ws.get("spsa.g", x.shape, f32)
+        s = spsa_scale(sp.d)
+        for i in range(q):
+            ops.spsa_probe(x, xp, xm, sp.d, sp.seed, sp.image0, sp.step, i)
+            self.objective(xp, ops.zero_(fp))
+            self.objective(xm, ops.zero_(fm))
+            last = i == q - 1
+            ops.spsa_accumulate_norms(g, fp, fm, l1 if last else None, l2sq if last else None, s,
+                                      sp.seed, sp.image0, sp.step, i, i == 0,
+                                      float(q) if last else 1.0, nonfinite=self.nonfinite)
+        return g
+
+    def step_spsa(self, x, m, momentum, a, e, sp, norm="linf"):
+        """One SPSA step on x in place (after prepare()): the estimate spsa_gradient(x, sp) takes
+        the update of ``norm`` unchanged — 'linf' the MIFGSM rule on the momentum buffer m
+        (ops.mi_update; momentum 0 is the plain sign step), 'l2' the PGDL2 rule (ops.l2_step,
+        ops.l2_project; m is not used). a, e in [-1,1] units."""
+        sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
+        if norm == "linf":
+            g = self.spsa_gradient(x, sp, l1=sums[0])
+            ops.mi_update(x, self.x0, g, sums[0], m, _f32(momentum), _f32(a), _f32(e),
+                          nonfinite=self.nonfinite)
+        elif norm == "l2":
+            g = self.spsa_gradient(x, sp, l2sq=sums[0])
+            ops.l2_step(x, self.x0, g, sums[0], sums[1], _f32(a), nonfinite=self.nonfinite)
+            ops.l2_project(x, self.x0, sums[1], _f32(e))
+        else:
+            raise ValueError("SPSA is implemented for norm='linf' and 'l2' only")
+        return x
+
+    def run_spsa(self, x0, t, steps, eps, alpha, momentum=0.0, norm="linf", random_start=False,
+                 start_noise=None, group=None, spsa_samples=16, spsa_delta=0.01, spsa_seed=0,
+                 spsa_first_image=0):
+        """SPSA, the score-based black-box attack: ``steps`` steps of step_spsa from x0, with
+        e = 2·eps, a = 2·alpha and the probe radius d = fp32(2·spsa_delta), ``spsa_samples`` = q
+        antithetic pairs per step (1 … SPSA_MAX_SAMPLES). The attack reads the objective's value
+        only — 2·q queries per image per step, self.spsa_queries = 2·q·steps in all — and no
+        gradient, so the loss scale plays no part; a non-finite objective raises as a non-finite
+        gradient does (_with_rescale). The directions are a pure function of (spsa_seed,
+        spsa_first_image + n, step, pair, element): reruns are bit-identical and an image's
+        result depends on neither the batch nor the world size. An estimate that is entirely
+        zero under 'linf' (every pair with f⁺ = f⁻) is reported like an overflow (0/0), as an
+        all-zero gradient is by run_mi."""
+        if norm not in ("linf", "l2"):
+            raise ValueError("SPSA is implemented for norm='linf' and 'l2' only")
+        q = _check_spsa_samples(spsa_samples)
+        d = _f32(2.0 * _check_spsa_delta(spsa_delta))
+        key = int(spsa_seed) % (1 << 64)
+        image0 = _check_spsa_first_image(spsa_first_image, x0.shape[0])
+        self.spsa_queries = 2 * q * int(steps)
+        return self._with_rescale(
+            lambda: self._run_spsa(x0, t, steps, eps, alpha, momentum, norm, random_start,
+                                   start_noise, q, d, key, image0), group)
+
+    def _run_spsa(self, x0, t, steps, eps, alpha, momentum, norm, random_start, start_noise, q, d,
+                  key, image0):
+        e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
+        x = self._start(x0, t, e, random_start, start_noise)
+        m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
+        for k in range(steps):
+            self.step_spsa(x, m, momentum, a, e, SpsaStep(q, d, key, image0, k), norm)
+        return x.clone()
+
     # ---- Auto-PGD ------------------------------------------------------------------------------
     def _apgd_buffers(self, shape, steps=None):
         """The workspace buffers ``apgd.*`` of a batch of ``shape`` (``steps``: of the attack that
@@ -822,6 +906,55 @@ def _check_vt_first_image(vt_first_image, n):
     return int(vt_first_image)
 
 
+SPSA_MAX_SAMPLES = 256  # antithetic pairs per step (torchattacks SPSA's default nb_sample is 128)
+# The Philox key of the SPSA directions is (seed + SPSA_SEED_OFFSET) mod 2^64 ("SPSA-ATK" in
+# ASCII): a stream of its own, like VT_SEED_OFFSET and DI_SEED_OFFSET.
+SPSA_SEED_OFFSET = 0x535053412D41544B
+# One SPSA step (step_spsa's ``sp``): the number of antithetic pairs q, the probe radius d in
+# [-1,1] units (fp32), the Philox key, the global index of the batch's first image and the
+# 0-based step index of the directions.
+SpsaStep = collections.namedtuple("SpsaStep", "samples d seed image0 step")
+
+
+def spsa_scale(d):
+    """s = 1/(2·d) of the SPSA estimate for a probe radius d, in fp32 arithmetic (2·d is exact,
+    one IEEE division)."""
+    return float(np.float32(1.0) / (np.float32(2.0) * np.float32(d)))
+
+
+def _check_spsa_samples(spsa_samples):
+    """attack()'s / run_spsa's ``spsa_samples``: an integer in 1 … SPSA_MAX_SAMPLES."""
+    if (isinstance(spsa_samples, (bool, np.bool_))
+            or not isinstance(spsa_samples, (int, np.integer))
+            or not 1 <= spsa_samples <= SPSA_MAX_SAMPLES):
+        raise ValueError(f"spsa_samples must be None or an integer in 1 … {SPSA_MAX_SAMPLES}")
+    return int(spsa_samples)
+
+
+def _check_spsa_delta(spsa_delta):
+    """attack()'s / run_spsa's ``spsa_delta``: finite and > 0, and so are the fp32 probe radius
+    d = fp32(2·spsa_delta) and its scale 1/(2·d) (both normal fp32 numbers)."""
+    ok = (not isinstance(spsa_delta, (bool, np.bool_)) and isinstance(spsa_delta, numbers.Real)
+          and np.isfinite(float(spsa_delta)) and float(spsa_delta) > 0)
+    if ok:
+        d = 2.0 * float(spsa_delta)
+        ok = 2.0 ** -126 <= d <= 2.0 ** 125
+    if not ok:
+        raise ValueError("spsa_delta must be a finite number > 0 (in [0,1] pixel units)")
+    return float(spsa_delta)
+
+
+def _check_spsa_first_image(spsa_first_image, n):
+    """The global index of imgs[0]: an integer >= 0 with spsa_first_image + n <= 2^32 (the image
+    word of the direction counter)."""
+    if (isinstance(spsa_first_image, (bool, np.bool_))
+            or not isinstance(spsa_first_image, (int, np.integer)) or spsa_first_image < 0):
+        raise ValueError("spsa_first_image must be an integer >= 0")
+    if int(spsa_first_image) + int(n) > 1 << 32:
+        raise ValueError("spsa_first_image + the batch size must be <= 2^32")
+    return int(spsa_first_image)
+
+
 def ti_gaussian_taps(kernlen=15, nsig=3.0):
     """The 1-D taps of torchattacks TIFGSM's Gaussian kernel, fp64: k/Σk with k = exp(−x²/2) on
     linspace(−nsig, nsig, kernlen). torchattacks' gkern (scipy.stats.norm.pdf, whose 1/√(2π)
@@ -964,7 +1097,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
            di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
-           vt_samples=None, vt_beta=1.5, vt_first_image=0, apgd=False):
+           vt_samples=None, vt_beta=1.5, vt_first_image=0, spsa_samples=None, spsa_delta=0.01,
+           spsa_first_image=0, apgd=False):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -1066,6 +1200,33 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     vt_first_image  the global index of imgs[0] (default 0), an integer ≥ 0: image n draws the
             noise of image vt_first_image + n, so attacking a slice of a batch with its offset
             gives the rows of the whole batch (``dist.attack_distributed`` passes the shard's).
+    spsa_samples  None (default): white-box, every rule above reads ∇L. An integer q in 1 … 256
+            (SPSA_MAX_SAMPLES), with norm='linf' or 'l2': SPSA, the score-based BLACK-BOX attack
+            (Spall 1992; Uesato et al. 2018; torchattacks SPSA's estimator). The attacker sees
+            the objective's value only: no backward pass runs. Per step k, with q antithetic
+            pairs i = 0 … q − 1 and d = fp32(2·spsa_delta):
+                      v_{k,i} = ±1 per element (Rademacher)
+                      x⁺ = clamp(x + d·v, −1, 1);  x⁻ = clamp(x − d·v, −1, 1)
+                      ĝ = (1/q)·Σ_i ((L(x⁺) − L(x⁻))/(2·d))·v_{k,i}
+            and ĝ takes the update of ``norm`` unchanged: 'linf' the MIFGSM rule (momentum=None
+            means μ = 0, the plain sign step), 'l2' the PGDL2 rule. 2·q queries per image per
+            step (info["queries"] = 2·q·steps); expect the step to cost 2·q forward passes. The
+            directions are counter-based and stateless (Philox4x32-10 in the HIP kernels, bit 31
+            of the element's word): a pure function of (seed, global image index, k, i, element
+            index), keyed with (seed + SPSA_SEED_OFFSET) mod 2^64, never stored — one fused
+            kernel writes both probes and another regenerates v while it accumulates. Reruns are
+            bit-identical, there is no host synchronisation, and an image's result depends on
+            neither the batch nor the world size. torchattacks SPSA feeds the same estimate to
+            Adam; here it feeds the project's own updates. It does not combine with nesterov,
+            ti_kernel, di_prob / di_schedule, si_scales, vt_samples or apgd: each of those
+            transforms or reuses a true gradient. A non-finite objective raises
+            FloatingPointError; so does, under 'linf', a step whose pairs all return
+            L(x⁺) = L(x⁻) exactly (an all-zero estimate, 0/0).
+    spsa_delta  the probe radius in [0,1] pixel units (default 0.01, torchattacks' delta), finite
+            and > 0. The probes are clamped to valid images but not to the ε-ball.
+    spsa_first_image  the global index of imgs[0] (default 0), an integer ≥ 0: image n takes the
+            directions of image spsa_first_image + n (``dist.attack_distributed`` passes the
+            shard's), as vt_first_image.
     apgd    False (default). True, with norm='linf' only (the L2 form is not implemented):
             Auto-PGD (Croce & Hein 2020; torchattacks APGD with norm='Linf', eot_iter=1, one
             run) on the objective, AttackEngine.run_apgd. ``alpha`` is not used: every image has
@@ -1143,11 +1304,28 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             raise ValueError("vt_samples (VMI-FGSM) is implemented for norm='linf' only")
     vt_beta = _check_vt_beta(vt_beta)
     _check_vt_first_image(vt_first_image, 0)
+    n_spsa = None
+    if spsa_samples is not None:
+        n_spsa = _check_spsa_samples(spsa_samples)
+        if norm not in ("linf", "l2"):
+            raise ValueError("spsa_samples (SPSA) is implemented for norm='linf' and 'l2' only")
+        mixed = [name for name, on in (
+            ("nesterov", nesterov), ("ti_kernel", ti_kernel is not None),
+            ("di_prob", di_prob is not None), ("di_schedule", di_schedule is not None),
+            ("si_scales", si_scales is not None), ("vt_samples", vt_samples is not None),
+            ("apgd", apgd)) if on]
+        if mixed:
+            raise ValueError(f"spsa_samples (SPSA) does not combine with {', '.join(mixed)}: "
+                             "they transform or reuse a true gradient, SPSA reads the "
+                             "objective's value only")
+    spsa_delta = _check_spsa_delta(spsa_delta)
+    _check_spsa_first_image(spsa_first_image, 0)
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
     _check_images(imgs, size, "imgs")
     vt_first_image = _check_vt_first_image(vt_first_image, imgs.shape[0])
+    spsa_first_image = _check_spsa_first_image(spsa_first_image, imgs.shape[0])
     if target is None:
         target = getattr(net, "default_target", None)
     if target is None:
@@ -1193,7 +1371,13 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != tuple(x0.shape):
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if apgd:
+    if n_spsa is not None:
+        adv = eng.run_spsa(x0, t, int(steps), float(eps), float(alpha),
+                           float(momentum) if momentum is not None else 0.0, norm, random_start,
+                           noise, group=group, spsa_samples=n_spsa, spsa_delta=spsa_delta,
+                           spsa_seed=(int(seed) + SPSA_SEED_OFFSET) % (1 << 64),
+                           spsa_first_image=spsa_first_image)
+    elif apgd:
         adv = eng.run_apgd(x0, t, int(steps), float(eps), random_start, noise, group=group)
     elif norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
                              or n_si > 1 or n_vt is not None):
@@ -1221,7 +1405,10 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     di_resize_rate=di_resize_rate if di_prob is not None else None,
                     di_applied=int(di[:, 3].sum()) if di is not None else 0,
                     si_scales=si_scales, nesterov=nesterov, vt_samples=vt_samples,
-                    vt_beta=vt_beta if vt_samples is not None else None)
+                    vt_beta=vt_beta if vt_samples is not None else None,
+                    spsa_samples=spsa_samples,
+                    spsa_delta=spsa_delta if spsa_samples is not None else None,
+                    queries=2 * n_spsa * int(steps) if n_spsa is not None else 0)
         if apgd:
             info["apgd"] = eng.apgd_info()
         return adv, info
@@ -1231,7 +1418,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
 def fgsm(net, imgs, eps, **kw):
     """FGSM = one PGD step with α = ε and no random start. Every other keyword is forwarded
     unchanged (nesterov's look-ahead is a no-op at the only step, where the momentum is 0; so is
-    vt_samples, whose variance term is 0 there: plain FGSM). ``apgd=True`` is rejected: one step
+    vt_samples, whose variance term is 0 there: plain FGSM; ``spsa_samples=q`` is the one-step
+    black-box form, the sign of the SPSA estimate). ``apgd=True`` is rejected: one step
     of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM."""
     if kw.get("apgd"):
         raise ValueError("fgsm() takes no apgd: one step of Auto-PGD is not FGSM; call "

@@ -528,6 +528,41 @@ int mia_vt_neighbor(const float* x, const float* m, float* y, int N, int64_t pla
  * (NULL or int[N]) is set for an image with a non-finite element of gt or of the new v. */
 int mia_vt_combine_norms(const float* g, const float* gv, float* v, float* gt, float* l1, int N,
                          int64_t plane, int* nonfinite, void* stream);
+/* SPSA (Spall 1992; Uesato et al. 2018; the estimator of torchattacks SPSA), a score-based
+ * black-box attack, images in [-1,1]: the gradient is estimated from objective values at
+ * antithetic probes along Rademacher directions. The direction of element i of image n, for
+ * (step, sample):
+ *   b[0..3] = Philox4x32-10(counter = (i / 4, image0 + n, step, sample),
+ *                           key = (seed & 0xffffffff, seed >> 32))      (as mia_vt_neighbor)
+ *   v = bit 31 of b[i % 4] is 0 ? +1 : −1
+ * — a pure function of (seed, image0 + n, step, sample, i): never stored, mia_spsa_probe and
+ * mia_spsa_accumulate_norms each regenerate it. The two probes of one pair, per element:
+ *   t = v > 0 ? d : −d;  yp = clamp(x + t, lo, hi);  ym = clamp(x − t, lo, hi)
+ * (torchattacks SPSA: x ± delta·v, here clamped so that a query is a valid image). x, yp, ym:
+ * fp32, N images of `plane` elements, three distinct buffers; N in 1 … 65535, plane < 2^31,
+ * image0 + N ≤ 2^32, d finite and > 0, lo ≤ hi (anything else: MIA_EINVAL before any launch).
+ * One launch, one read of x, one fp32 rounding per operation; the vector and scalar forms (as
+ * mia_vt_neighbor) give the same bits. */
+int mia_spsa_probe(const float* x, float* yp, float* ym, int N, int64_t plane, float d, float lo,
+                   float hi, uint64_t seed, uint32_t image0, uint32_t step, uint32_t sample,
+                   void* stream);
+/* One pair's term into the step's estimate ĝ = (1/q)·Σ_i c_i·v_i (torchattacks SPSA:
+ * df / (2·delta) · v averaged over the samples), with the per-image norms of the result:
+ *   c = (fp[n] − fm[n])·s   (s = 1/(2·d); the difference rounded, then the product)
+ *   t = v > 0 ? c : −c;  r = first ? t : acc + t;  div ≠ 1: r = r / div (IEEE division);  acc = r
+ *   l1[n] += Σ|r_n|,  l2sq[n] += Σ r_n²   (fp32 [N], either may be NULL; ordered reductions as in
+ *   mia_si_accumulate_norms).
+ * acc: fp32, N images of `plane` elements, not read when first ≠ 0; fp, fm: fp32 [N] in device
+ * memory, the objective at yp and ym; acc, fp and fm distinct; s finite and > 0, div finite and
+ * > 0 (the caller passes q on the last pair, 1 before), N, plane and image0 as above (anything
+ * else: MIA_EINVAL before any launch). The vector (plane % 4 == 0, 16-byte aligned acc) and scalar
+ * forms give the same bits, sums included; reruns are bit-identical and an image's acc and sums do
+ * not depend on the other images. nonfinite (NULL or int[N]) is set for an image with a
+ * non-finite element of r: a non-finite objective arrives there through c. */
+int mia_spsa_accumulate_norms(float* acc, const float* fp, const float* fm, float* l1, float* l2sq,
+                              int N, int64_t plane, float s, uint64_t seed, uint32_t image0,
+                              uint32_t step, uint32_t sample, int first, float div, int* nonfinite,
+                              void* stream);
 /* Auto-PGD (Croce & Hein 2020; torchattacks APGD.attack_single_run, norm = 'Linf', eot_iter = 1)
  * on cost = −L, images in [-1,1]: three launches per step, all decisions on the device. Per-image
  * state is written by mia_apgd_decide alone (one thread per image) and only read by the other

@@ -256,6 +256,79 @@ int main() {
                                        nullptr, nullptr), "si acc N");
   expect_error(mia_si_accumulate_norms(di_a, di_b, dummy, dummy, 2, -1, 0.5f, 0, 1.f, nullptr,
                                        nullptr), "si acc plane < 0");
+  // SPSA: null / aliased / overlapping buffers, the probe radius, the scale, the divisor, sizes
+  // and the image word (2 images of 48 floats per buffer: di_a, di_b and sp_c are disjoint;
+  // sp_f holds fp at 0 and fm at 8)
+  float sp_buf[128];
+  float sp_f[16];
+  float* sp_c = sp_buf;
+  expect_error(mia_spsa_probe(nullptr, di_b, sp_c, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe null x");
+  expect_error(mia_spsa_probe(di_a, nullptr, sp_c, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe null yp");
+  expect_error(mia_spsa_probe(di_a, di_b, nullptr, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe null ym");
+  expect_error(mia_spsa_probe(di_a, di_a, sp_c, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe yp is x");
+  expect_error(mia_spsa_probe(di_a, di_b, di_a, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe ym is x");
+  expect_error(mia_spsa_probe(di_a, di_b, di_b, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe ym is yp");
+  expect_error(mia_spsa_probe(di_a, di_b, di_b + 95, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe ym overlaps yp");
+  expect_error(mia_spsa_probe(di_a + 1, di_a, sp_c, 2, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe overlap back");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 48, 0.f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe d 0");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 48, -0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe d < 0");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 48, INFINITY, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe d inf");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 48, nanf(""), -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe d nan");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 48, 0.02f, 1.f, -1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe lo > hi");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 0, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe N 0");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 1 << 16, 48, 0.02f, -1.f, 1.f, 5, 0, 0, 0,
+                              nullptr), "spsa probe N");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 0, 0.02f, -1.f, 1.f, 5, 0, 0, 0, nullptr),
+               "spsa probe plane 0");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 1LL << 31, 0.02f, -1.f, 1.f, 5, 0, 0, 0,
+                              nullptr), "spsa probe plane 2^31");
+  expect_error(mia_spsa_probe(di_a, di_b, sp_c, 2, 48, 0.02f, -1.f, 1.f, 5, 0xffffffffu, 0, 0,
+                              nullptr), "spsa probe image0 + N > 2^32");
+  expect_error(mia_spsa_accumulate_norms(nullptr, sp_f, sp_f + 8, dummy, dummy, 2, 48, 25.f, 5, 0,
+                                         0, 0, 1, 1.f, nullptr, nullptr), "spsa acc null acc");
+  expect_error(mia_spsa_accumulate_norms(di_a, nullptr, sp_f + 8, dummy, dummy, 2, 48, 25.f, 5, 0,
+                                         0, 0, 1, 1.f, nullptr, nullptr), "spsa acc null fp");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, nullptr, nullptr, nullptr, 2, 48, 25.f, 5, 0,
+                                         0, 0, 1, 1.f, nullptr, nullptr), "spsa acc null fm");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f, dummy, dummy, 2, 48, 25.f, 5, 0, 0, 0,
+                                         1, 1.f, nullptr, nullptr), "spsa acc fm is fp");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 1, dummy, dummy, 2, 48, 25.f, 5, 0, 0,
+                                         0, 1, 1.f, nullptr, nullptr), "spsa acc fm overlaps fp");
+  expect_error(mia_spsa_accumulate_norms(di_a, di_a + 95, sp_f, dummy, dummy, 2, 48, 25.f, 5, 0,
+                                         0, 0, 1, 1.f, nullptr, nullptr), "spsa acc fp inside acc");
+  expect_error(mia_spsa_accumulate_norms(di_a + 1, sp_f, di_a, dummy, dummy, 2, 48, 25.f, 5, 0, 0,
+                                         0, 1, 1.f, nullptr, nullptr), "spsa acc inside fm");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, 0.f, 5, 0, 0,
+                                         0, 1, 1.f, nullptr, nullptr), "spsa acc s 0");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, INFINITY, 5,
+                                         0, 0, 0, 1, 1.f, nullptr, nullptr), "spsa acc s inf");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, nanf(""), 5,
+                                         0, 0, 0, 1, 1.f, nullptr, nullptr), "spsa acc s nan");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, 25.f, 5, 0, 0,
+                                         0, 1, 0.f, nullptr, nullptr), "spsa acc div 0");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, 25.f, 5, 0, 0,
+                                         0, 1, nanf(""), nullptr, nullptr), "spsa acc div nan");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 70000, 48, 25.f, 5,
+                                         0, 0, 0, 1, 1.f, nullptr, nullptr), "spsa acc N");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, -1, 25.f, 5, 0, 0,
+                                         0, 1, 1.f, nullptr, nullptr), "spsa acc plane < 0");
+  expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, 25.f, 5,
+                                         0xffffffffu, 0, 0, 1, 1.f, nullptr, nullptr),
+               "spsa acc image0 + N > 2^32");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
