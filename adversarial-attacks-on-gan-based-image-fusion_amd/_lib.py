@@ -157,6 +157,8 @@ SIGNATURES = {
     "mia_spsa_accumulate_norms": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, ctypes.c_uint64,
                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int,
                                           c_float, P, P]),
+    "mia_uap_accumulate": (c_int, [P, P, P, c_int, c_int64, c_int, P, P]),
+    "mia_uap_step": (c_int, [P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float, P]),
     "mia_apgd_update": (c_int, [P, P, P, P, P, c_int, c_int64, c_float, c_float, c_float, c_float,
                                 P, P]),
     "mia_apgd_decide": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),

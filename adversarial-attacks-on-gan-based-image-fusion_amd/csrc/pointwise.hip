@@ -1431,6 +1431,143 @@ __global__ __launch_bounds__(TPB) void spsa_accumulate_norms_kernel(
   block_slot_store<2>(lane_sum<4>(a1), lane_sum<4>(a2), part);
 }
 
+// ---- Universal perturbation: ONE δ plane for all images, updated from the sign of an exact
+// integer sum over the images. Both kernels run on a 1-D grid over the groups of 4 consecutive
+// plane elements (VEC / guarded scalars as above: the same bits); the thread that owns a group
+// walks the images, UAP_UNROLL loads in flight.
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+constexpr int UAP_UNROLL = 8;
+constexpr float UAP_ONE = 16777216.f;  // 2^24, the fixed point of the per-image terms
+
+template <bool VEC>
+__device__ __forceinline__ void ld4i(const long long* __restrict__ p, int cnt, long long (&v)[4]) {
+  if (VEC) {
+    const i64x2 a = *(const i64x2*)p, b = *(const i64x2*)(p + 2);
+    v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = e < cnt ? p[e] : 0;
+  }
+}
+
+// Per image n and element j:  ĝ = (−g) / (l1[n] / plane)  (mia_mi_update's normalisation, the same
+// bits);  q = (int64) rint(ĝ·2^24)  (the product is exact, rint is round-half-even, and the result
+// is an integer fp32 holds exactly);  acc_j = (first ? 0 : acc_j) + Σ_n q_n,j.
+// |ĝ| < 2·plane is the range the caller's bound rests on: an element outside it (NaN and ±Inf
+// included) marks its image and contributes 0. Integer sums are associative, so neither the order
+// of the images nor the split over calls, blocks or ranks can change a bit. gridDim.y = 1: the
+// thread owns its group and stores it. gridDim.y > 1 (the image-split form, MIA_UAP_SPLIT): block
+// row y sums a contiguous share of the images and adds it with 64-bit vector integer atomics to an
+// acc the launcher zeroed when first.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void uap_accumulate_kernel(
+    const float* __restrict__ g, const float* __restrict__ l1, long long* __restrict__ acc, int N,
+    int64_t plane, int first, int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  const int64_t ng = (plane + 3) / 4;
+  const float fplane = (float)plane, lim = 2.f * fplane;
+  const int share = (N + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int n_lo = (int)blockIdx.y * share, n_hi = n_lo + share < N ? n_lo + share : N;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = j * 4;
+    const int cnt = (int)(plane - i0 < 4 ? plane - i0 : 4);
+    long long s[4] = {0, 0, 0, 0};
+    for (int n0 = n_lo; n0 < n_hi; n0 += UAP_UNROLL) {
+      float v[UAP_UNROLL][4], mean[UAP_UNROLL];
+#pragma unroll
+      for (int u = 0; u < UAP_UNROLL; ++u)
+        if (n0 + u < n_hi) {
+          ld4<VEC>(g + (int64_t)(n0 + u) * plane + i0, cnt, v[u]);
+          mean[u] = l1[n0 + u] / fplane;
+        }
+#pragma unroll
+      for (int u = 0; u < UAP_UNROLL; ++u)
+        if (n0 + u < n_hi) {
+          bool bad = false;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float gh = (-v[u][e]) / mean[u];
+            const bool ok = fabsf(gh) < lim;  // false for NaN
+            bad |= !ok && e < cnt;
+            const float p = gh * UAP_ONE;
+            s[e] += ok ? (long long)__builtin_rintf(p) : 0LL;
+          }
+          if (bad && nonfinite) nonfinite[n0 + u] = 1;
+        }
+    }
+    if (gridDim.y > 1) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (e < cnt) atomicAdd((unsigned long long*)(acc + i0 + e), (unsigned long long)s[e]);
+      continue;
+    }
+    if (!first) {
+      long long old[4];
+      ld4i<VEC>(acc + i0, cnt, old);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] += old[e];
+    }
+    if (VEC) {
+      i64x2 a, b;
+      a[0] = s[0], a[1] = s[1], b[0] = s[2], b[1] = s[3];
+      *(i64x2*)(acc + i0) = a;
+      *(i64x2*)(acc + i0 + 2) = b;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (e < cnt) acc[i0 + e] = s[e];
+    }
+  }
+}
+
+// δ_j ← clamp(δ_j + a·sgn(acc_j), −e, e)  (sgn(0) = 0; acc = nullptr: δ is only read), then for
+// every image x_n,j = clamp(x0_n,j + δ_j, lo, hi), in one pass. One fp32 rounding per operation
+// (a·sgn is exact). N = 0: δ only.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void uap_step_kernel(float* __restrict__ delta,
+                                                       const long long* __restrict__ acc,
+                                                       float* __restrict__ x,
+                                                       const float* __restrict__ x0, int N,
+                                                       int64_t plane, float a, float e, float lo,
+                                                       float hi) {
+#pragma clang fp contract(off)
+  const int64_t ng = (plane + 3) / 4;
+  for (int64_t j = blockIdx.x * (int64_t)TPB + threadIdx.x; j < ng; j += (int64_t)gridDim.x * TPB) {
+    const int64_t i0 = j * 4;
+    const int cnt = (int)(plane - i0 < 4 ? plane - i0 : 4);
+    float d[4];
+    ld4<VEC>(delta + i0, cnt, d);
+    if (acc) {
+      long long A[4];
+      ld4i<VEC>(acc + i0, cnt, A);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float sg = A[k] > 0 ? 1.f : (A[k] < 0 ? -1.f : 0.f);
+        const float s = a * sg;
+        const float t = d[k] + s;
+        d[k] = fminf(fmaxf(t, -e), e);
+      }
+      st4<VEC>(delta + i0, cnt, d);
+    }
+    for (int n0 = 0; n0 < N; n0 += UAP_UNROLL) {
+      float v[UAP_UNROLL][4];
+#pragma unroll
+      for (int u = 0; u < UAP_UNROLL; ++u)
+        if (n0 + u < N) ld4<VEC>(x0 + (int64_t)(n0 + u) * plane + i0, cnt, v[u]);
+#pragma unroll
+      for (int u = 0; u < UAP_UNROLL; ++u)
+        if (n0 + u < N) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float r = v[u][k] + d[k];
+            v[u][k] = fminf(fmaxf(r, lo), hi);
+          }
+          st4<VEC>(x + (int64_t)(n0 + u) * plane + i0, cnt, v[u]);
+        }
+    }
+  }
+}
+
 // ---- Auto-PGD (Croce & Hein 2020; torchattacks APGD.attack_single_run, norm = 'Linf') on
 // cost = −L. Three kernels per step. The update and the copies run on the SI kernels' (slots, N)
 // grid, a thread owning one group of 4 consecutive elements of its image, so VEC and the guarded
@@ -2791,6 +2928,75 @@ extern "C" int mia_spsa_accumulate_norms(float* acc, const float* fp, const floa
                        r.part, plane, s, k0, k1, image0, step, sample, first != 0, div, nonfinite);
   rc = check_launch("spsa_accumulate_norms_kernel");
   return rc != MIA_OK ? rc : red_finish(r, st);
+}
+
+// Block rows of mia_uap_accumulate's grid: 1 = the loop form (a thread walks all N images and
+// stores its group), > 1 = the image-split form on integer atomics. Both are exact; DESIGN.md
+// records the A/B behind the default.
+#ifndef MIA_UAP_SPLIT
+#define MIA_UAP_SPLIT 1
+#endif
+
+static inline bool byte_overlap(const void* a, int64_t la, const void* b, int64_t lb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb ? pb - pa < (uintptr_t)la : pa - pb < (uintptr_t)lb;
+}
+
+extern "C" int mia_uap_accumulate(const float* g, const float* l1, int64_t* acc, int N,
+                                  int64_t plane, int first, int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(g && l1 && acc, "null g / l1 / acc");
+  MIA_CHECK_IMAGES(N, plane);
+  // |ĝ| < 2·plane (the kernel drops anything else), so |q| = |rint(ĝ·2^24)| ≤ 2^25·plane and the
+  // sum over n images stays below n·plane·2^25 < 2^62 for n·plane < 2^37: no int64 overflow, with
+  // a factor 2 to spare for the fp32 rounding of 2·plane. The same bound holds job-wide when the
+  // caller adds the planes of several calls or ranks (attack() checks it with the job's n).
+  MIA_CHECK_ARG((int64_t)N * plane < (1LL << 37), "N * plane must be < 2^37");
+  MIA_CHECK_ARG(((uintptr_t)acc & 7) == 0, "acc must be 8-byte aligned");
+  const int64_t gb = (int64_t)N * plane * 4, ab = plane * 8, lb = (int64_t)N * 4;
+  MIA_CHECK_ARG(!byte_overlap(g, gb, acc, ab) && !byte_overlap(l1, lb, acc, ab) &&
+                    !byte_overlap(g, gb, l1, lb) &&
+                    !(nonfinite && (byte_overlap(nonfinite, lb, acc, ab) ||
+                                    byte_overlap(nonfinite, lb, g, gb) ||
+                                    byte_overlap(nonfinite, lb, l1, lb))),
+                "g, l1, acc and nonfinite must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(g) && aligned16(acc);
+  const int rows = MIA_UAP_SPLIT < N ? MIA_UAP_SPLIT : N;
+  const dim3 grid(blocks_for((plane + 3) / 4, TPB), rows);
+  if (rows > 1 && first) {
+    const int rc = mia_memset(acc, 0, ab, stream);
+    if (rc != MIA_OK) return rc;
+  }
+  if (vec)
+    MIA_LAUNCH(uap_accumulate_kernel<true>, grid, dim3(TPB), 0, g, l1, (long long*)acc, N, plane,
+               first != 0, nonfinite);
+  MIA_LAUNCH(uap_accumulate_kernel<false>, grid, dim3(TPB), 0, g, l1, (long long*)acc, N, plane,
+             first != 0, nonfinite);
+}
+
+extern "C" int mia_uap_step(float* delta, const int64_t* acc, float* x, const float* x0, int N,
+                            int64_t plane, float a, float e, float lo, float hi, void* stream) {
+  MIA_CHECK_ARG(delta, "null delta");
+  MIA_CHECK_ARG(N >= 0 && N <= 65535, "N must be in 0 … 65535");
+  MIA_CHECK_ARG(plane > 0 && plane < (1LL << 31), "plane must be in 1 … 2^31 − 1");
+  MIA_CHECK_ARG(N > 0 ? (x && x0) : (!x && !x0), "x and x0: both for N > 0, both NULL for N = 0");
+  MIA_CHECK_ARG(N > 0 || acc, "nothing to do: N = 0 and acc = NULL");
+  MIA_CHECK_ARG(a >= 0.f && e > 0.f && lo <= hi, "need a >= 0, e > 0 and lo <= hi");
+  MIA_CHECK_ARG(!acc || ((uintptr_t)acc & 7) == 0, "acc must be 8-byte aligned");
+  const int64_t xb = (int64_t)N * plane * 4, db = plane * 4, ab = plane * 8;
+  MIA_CHECK_ARG(!(acc && byte_overlap(delta, db, acc, ab)), "delta and acc must be distinct");
+  if (N > 0)
+    MIA_CHECK_ARG(!byte_overlap(x, xb, x0, xb) && !byte_overlap(x, xb, delta, db) &&
+                      !byte_overlap(x0, xb, delta, db) &&
+                      !(acc && (byte_overlap(x, xb, acc, ab) || byte_overlap(x0, xb, acc, ab))),
+                  "delta, acc, x and x0 must be distinct buffers");
+  const bool vec = plane % 4 == 0 && aligned16(delta) && (!acc || aligned16(acc)) &&
+                   (N == 0 || (aligned16(x) && aligned16(x0)));
+  const dim3 grid(blocks_for((plane + 3) / 4, TPB));
+  if (vec)
+    MIA_LAUNCH(uap_step_kernel<true>, grid, dim3(TPB), 0, delta, (const long long*)acc, x, x0, N,
+               plane, a, e, lo, hi);
+  MIA_LAUNCH(uap_step_kernel<false>, grid, dim3(TPB), 0, delta, (const long long*)acc, x, x0, N,
+             plane, a, e, lo, hi);
 }
 
 extern "C" int mia_apgd_update(float* x, float* x_old, const float* x0, const float* g,

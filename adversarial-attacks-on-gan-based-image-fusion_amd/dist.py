@@ -4,10 +4,13 @@ Images are independent, so the batch is split into contiguous shards, one per ra
 per GPU, ``torch.distributed`` with the ``nccl`` backend = RCCL over xGMI). Every rank runs the
 whole PGD loop on its shard with no collective in the data path; the only exchange is ONE
 ``all_gather_into_tensor`` of the final adversarial images (shards padded to equal size).
+The one exception is the universal perturbation (``universal=True``), whose images share one δ:
+it adds one all-reduce of an int64 plane per step, exact in any order.
 The reference itself is single-GPU (``device = "cuda:0"``, attack_main2.py:843).
 """
 import numbers
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -77,7 +80,20 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       of the full batch, and the output does not depend on the world size.
     * Auto-PGD (``apgd=True``) needs nothing more: its step sizes, counters and best iterates
       are per image and live on the shard's device, and its only random state is the start
-      noise sliced above, so the output does not depend on the world size."""
+      noise sliced above, so the output does not depend on the world size.
+    * The universal perturbation (``universal=True``) is the one attack whose images are not
+      independent, and the one attack with a collective per step: every step all-reduces (SUM)
+      the int64 plane of the summed normalised gradients over ``group``
+      (``pgd.uap_all_reduce``; on the device for nccl, through a CPU copy for gloo). Integer sums
+      are associative, so δ and the output do not depend on the world size, bit for bit. The
+      start noise is ONE (1,3,S,S) draw from ``seed``, the same on every rank and not sliced.
+      The range check counts the full batch (``pgd.check_universal_count``). A rank with an
+      empty shard joins every step's all-reduce with a zero plane and applies the sum to a δ of
+      its own (``pgd.idle_rank_universal``), then joins the status round, so no rank blocks and
+      every rank ends with the same δ. With ``universal=True`` only, ``return_info=True`` is
+      accepted and returns (the gathered batch, this rank's info): ``info["universal"]`` holds
+      δ on every rank, the other entries describe the rank's own shard (an empty shard's info
+      holds ``universal`` alone)."""
     from . import pgd
     group = group if group is not None else dist.group.WORLD
     world = dist.get_world_size(group)
@@ -85,13 +101,31 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     n = imgs.shape[0]
     lo, hi = shard_bounds(n, world, rank)
     gather_dev = torch.device("cpu") if dist.get_backend(group) == "gloo" else net.decoder.device
-    if hi == lo:
-        pgd.idle_rank_consensus(group)
-        local = torch.zeros((0,) + tuple(imgs.shape[1:]), dtype=torch.float32, device=gather_dev)
-        return gather_shards(local, n, group).to(imgs.device)
-    tgt = target if target.shape[0] == 1 else target[lo:hi]
+    universal = kw.get("universal", False)  # anything but a bool: attack() rejects it
+    universal = isinstance(universal, (bool, np.bool_)) and bool(universal)
+    want_info = universal and bool(kw.get("return_info", False))
     noise = None
-    if random_start:
+    if universal:
+        pgd.check_universal_count(n, imgs[0].numel() if n else 0)
+        if random_start:  # one draw for the shared δ, the same on every rank: not sliced
+            noise = kw.pop("start_noise", None)
+            if noise is None:
+                noise = pgd.make_start_noise((1,) + tuple(imgs.shape[1:]), seed, "linf")
+    if hi == lo:
+        info = None
+        if universal:
+            delta = pgd.idle_rank_universal(group, int(steps), (1,) + tuple(imgs.shape[1:]), eps,
+                                            kw.get("alpha", 0.01), net.decoder.device,
+                                            random_start, noise)
+            delta = delta.to(imgs.device)
+            info = dict(universal=dict(delta=delta, linf=float(delta.abs().max())))
+        else:
+            pgd.idle_rank_consensus(group)
+        local = torch.zeros((0,) + tuple(imgs.shape[1:]), dtype=torch.float32, device=gather_dev)
+        out = gather_shards(local, n, group).to(imgs.device)
+        return (out, info) if want_info else out
+    tgt = target if target.shape[0] == 1 else target[lo:hi]
+    if random_start and not universal:
         noise_norm = "l2" if kw.get("norm", "linf") == "l2" else "linf"
         noise = pgd.make_start_noise(tuple(imgs.shape), seed, noise_norm)[lo:hi]
     if "vt_samples" in kw or "vt_first_image" in kw:
@@ -104,4 +138,8 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
             kw = dict(kw, spsa_first_image=int(first) + lo)
     local = pgd.attack(net, imgs[lo:hi], eps, steps, target=tgt, random_start=random_start,
                        seed=seed, start_noise=noise, group=group, **kw)
-    return gather_shards(local.to(gather_dev, torch.float32), n, group).to(imgs.device)
+    info = None
+    if want_info:
+        local, info = local
+    out = gather_shards(local.to(gather_dev, torch.float32), n, group).to(imgs.device)
+    return (out, info) if want_info else out

@@ -851,6 +851,77 @@ def spsa_accumulate_norms(acc, fp, fm, l1, l2sq, s, seed, image0, step, sample, 
     return acc
 
 
+UAP_MAX_ELEMENTS = 1 << 37  # mia_uap_accumulate: images × plane elements summed into one plane
+
+
+def _uap_plane(t, dtype, name, plane=None):
+    """A shared plane of the universal perturbation: a non-empty tensor of ``dtype`` (with
+    ``plane`` elements, if given). Returns its element count."""
+    if t is None or not torch.is_tensor(t) or t.dtype != dtype or t.numel() == 0:
+        raise ValueError(f"{name} must be a non-empty {dtype} tensor")
+    if plane is not None and t.numel() != plane:
+        raise ValueError(f"{name}: numel {t.numel()} != {plane} (one plane)")
+    return t.numel()
+
+
+def uap_accumulate(g, l1, acc, first, nonfinite=None):
+    """acc[j] ← (first ? 0 : acc[j]) + Σ_n rint(((−g[n][j]) / (l1[n]/plane))·2^24) as int64: the
+    per-image normalised gradients (mi_update's normalisation) into the exact integer sum a
+    universal perturbation steps along (mia_uap_accumulate). g: a non-empty fp32 batch of N ≤ 65535
+    images; l1: fp32 (N,), Σ|g_n|; acc: int64, one plane; N·plane < 2^37. An element of the
+    normalised gradient outside ±2·plane (NaN, ±Inf) marks nonfinite[n] and contributes 0."""
+    if g is None or g.dim() < 2 or g.dtype != torch.float32 or g.numel() == 0:
+        raise ValueError("g must be a non-empty fp32 batch of images")
+    N, plane = g.shape[0], g.numel() // g.shape[0]
+    _need(l1, (N,), torch.float32, "l1")
+    _uap_plane(acc, torch.int64, "acc", plane)
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    _distinct([("g", g), ("l1", l1), ("acc", acc)]
+              + ([("nonfinite", nonfinite)] if nonfinite is not None else []))
+    if N > 65535:
+        raise ValueError("at most 65535 images per call")
+    if N * plane >= UAP_MAX_ELEMENTS:
+        raise ValueError("N * plane must be < 2^37 (the int64 sum's range)")
+    call("mia_uap_accumulate", ptr(g), ptr(l1), ptr(acc), N, plane, 1 if first else 0,
+         ptr(nonfinite), stream())
+    return acc
+
+
+def uap_step(delta, acc, x, x0, a, e, lo=-1.0, hi=1.0):
+    """delta ← clamp(delta + a·sgn(acc), −e, e) (sgn(0) = 0), then x[n] ← clamp(x0[n] + delta, lo,
+    hi) for every image, in one pass (mia_uap_step). acc None: delta is applied as it is. x and x0
+    both None: delta is updated only (a rank with an empty shard; needs acc). delta: fp32, one
+    plane; acc: int64, one plane; x, x0: distinct fp32 batches of one shape; a finite and >= 0,
+    e finite and > 0, lo <= hi."""
+    plane = _uap_plane(delta, torch.float32, "delta")
+    if acc is not None:
+        _uap_plane(acc, torch.int64, "acc", plane)
+    if (x is None) != (x0 is None):
+        raise ValueError("x and x0 must both be given or both be None")
+    N = 0
+    bufs = [("delta", delta)] + ([("acc", acc)] if acc is not None else [])
+    if x0 is not None:
+        N, per = _si_images(x0, x, "x0", "x")
+        if per != plane:
+            raise ValueError(f"x0: {per} elements per image != {plane} (delta's plane)")
+        if N > 65535:
+            raise ValueError("at most 65535 images per call")
+        bufs += [("x", x), ("x0", x0)]
+    elif acc is None:
+        raise ValueError("nothing to do: no images and no acc")
+    _distinct(bufs)
+    for v, nm in ((a, "a"), (e, "e")):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+            raise ValueError(f"{nm} must be a finite number")
+    if a < 0 or e <= 0:
+        raise ValueError("need a >= 0 and e > 0")
+    if not float(lo) <= float(hi):
+        raise ValueError("need lo <= hi")
+    call("mia_uap_step", ptr(delta), ptr(acc), ptr(x), ptr(x0), N, plane, float(a), float(e),
+         float(lo), float(hi), stream())
+    return delta
+
+
 APGD_SAVE, APGD_RESTORE = 1, 2  # MIA_APGD_SAVE, MIA_APGD_RESTORE: the bits of an action word
 
 

@@ -71,6 +71,92 @@ def _f32(v):
     return float(np.float32(v))
 
 
+def uap_all_reduce(acc, group=None):
+    """The job-wide sum of the universal perturbation's int64 plane, in place: one
+    all_reduce(SUM) over ``group`` (none without a group). Integer addition is associative, so the
+    result does not depend on the reduction's order or on the world size. On the device for nccl;
+    through a CPU copy for gloo (as rescale_consensus chooses its device)."""
+    if group is None:
+        return acc
+    import torch.distributed as dist
+    if dist.get_backend(group) == "gloo":
+        host = acc.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        acc.copy_(host)
+    else:
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group)
+    return acc
+
+
+def check_universal_count(n_total, plane):
+    """The range of the universal perturbation's integer sum: per image and element the term is
+    q = rint(ĝ·2^24) with |ĝ| = |g|/mean|g| < 2·plane (|g_j| ≤ Σ|g| = plane·mean|g|, and the kernel
+    drops anything outside), so |q| ≤ 2^25·plane and |Σ_n q| ≤ n_total·plane·2^25. That stays
+    below 2^62 — inside int64 with a factor 2 to spare — for n_total·plane < 2^37, n_total counted
+    over the whole job (every rank's images enter the one sum)."""
+    if int(n_total) * int(plane) >= ops.UAP_MAX_ELEMENTS:
+        raise ValueError(f"universal: images × elements per image = {int(n_total)} × {int(plane)} "
+                         "must be < 2^37 (the range of the int64 sum over the images)")
+
+
+def idle_rank_universal(group, steps, shape, eps, alpha, device, random_start=False,
+                        start_noise=None):
+    """A rank with an empty shard in a universal attack (``shape`` = (1,3,S,S)): it joins every
+    step's all-reduce with a zero plane and applies the job's sum to a δ of its own
+    (ops.uap_step with no images), so it ends with the δ every other rank has; after each run of
+    ``steps`` steps it joins the status round, and re-runs from δ₀ with the others when they lower
+    the loss scale. ``steps`` all-reduces of the plane and one of the status per run. Returns δ."""
+    e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
+    plane = int(np.prod(shape))
+    zero_acc = torch.zeros(plane, dtype=torch.int64, device=device)
+    acc = torch.empty_like(zero_acc)
+    zero = torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+    noise = None
+    if random_start:
+        if start_noise is None or tuple(start_noise.shape) != tuple(shape):
+            raise ValueError("a universal start_noise must have the shape (1,3,S,S)")
+        noise = start_noise.to(device, torch.float32).contiguous()
+    while True:
+        delta = torch.zeros_like(zero)
+        if noise is not None:
+            ops.random_start(delta, zero, noise, e, -e, e)
+        for _ in range(int(steps)):
+            acc.copy_(zero_acc)
+            uap_all_reduce(acc, group)
+            ops.uap_step(delta, acc, None, None, a, e)
+        st = rescale_consensus(RUN_OK, group)
+        if st == RUN_OK:
+            return delta
+        if st == RUN_FATAL:
+            raise FloatingPointError("non-finite gradient on another rank")
+
+
+def apply_universal(imgs, delta):
+    """clamp(imgs + delta, −1, 1): a universal perturbation (``info["universal"]["delta"]`` of
+    ``attack(..., universal=True)``, (1,3,S,S)) applied to any images of its size, held-out ones
+    included, on the HIP kernel of the attack itself (ops.uap_step without a sum, bit-identical to
+    the attack's own application). imgs: (N,3,S,S) floating point, on CPU or GPU, not modified;
+    the computation runs on delta's device if that is a GPU, else on imgs', else (both on the
+    host, as ``attack`` returns them for host images) on the current GPU; without a GPU it raises.
+    Returns fp32 images on imgs' device."""
+    if not torch.is_tensor(delta) or delta.dim() != 4 or delta.shape[0] != 1 or delta.shape[1] != 3 \
+            or delta.shape[2] != delta.shape[3] or not delta.is_floating_point():
+        raise ValueError("delta must be a (1,3,S,S) floating point tensor")
+    _check_images(imgs, delta.shape[2], "imgs")
+    if imgs.shape[0] < 1:
+        raise ValueError("imgs must hold at least one image")
+    dev = delta.device if delta.is_cuda else imgs.device
+    if dev.type != "cuda":
+        if not torch.cuda.is_available():
+            raise ValueError("apply_universal runs on the GPU only, and there is none")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    x0 = imgs.detach().to(dev, torch.float32).contiguous()
+    d = delta.detach().to(dev, torch.float32).contiguous()
+    out = torch.empty_like(x0)
+    ops.uap_step(d, None, out, x0, 0.0, 1.0)
+    return out.to(imgs.device)
+
+
 class AttackEngine:
     """Owns the device networks and the step workspace for one (batch, size, dtype)."""
 
@@ -720,6 +806,77 @@ class AttackEngine:
             self.step_spsa(x, m, momentum, a, e, SpsaStep(q, d, key, image0, k), norm)
         return x.clone()
 
+    # ---- the universal perturbation: one δ for the whole batch --------------------------------
+    def _uap_buffers(self, shape):
+        """The workspace buffers ``uap.*`` of a batch of ``shape``: the shared plane ``delta``
+        (1,3,S,S) fp32, a zero plane of its shape (x0 of the random start) and the int64 sum
+        ``acc`` [3·S²]."""
+        ws, one = self.ws, (1,) + tuple(shape[1:])
+        plane = int(np.prod(shape[1:]))
+        return dict(delta=ws.get("uap.delta", one, torch.float32),
+                    zero=ws.get("uap.zero", one, torch.float32),
+                    acc=ws.get("uap.acc", (plane,), torch.int64))
+
+    def start_universal(self, x0, t, eps, random_start=False, start_noise=None):
+        """prepare(), δ₀ (0, or clamp(e·u, −e, e) for a random start with the ONE (1,3,S,S) draw
+        ``start_noise``: ops.random_start on a zero plane with the bounds ∓e) and the iterate
+        x = clamp(x0 + δ₀, −1, 1) (ops.uap_step without a sum). Returns the iterate buffer for
+        step_universal; δ lives in the workspace buffer ``uap.delta``."""
+        self.prepare(x0, t)
+        e = _f32(2.0 * eps)
+        b = self._uap_buffers(x0.shape)
+        delta, zero = ops.zero_(b["delta"]), ops.zero_(b["zero"])
+        if random_start:
+            if start_noise is None:
+                raise ValueError("random_start needs start_noise (make_start_noise)")
+            if tuple(start_noise.shape) != tuple(delta.shape):
+                raise ValueError("a universal start_noise must have the shape (1,3,S,S)")
+            ops.random_start(delta, zero, start_noise, e, -e, e)
+        x = self.ws.get("adv", x0.shape, torch.float32)
+        ops.uap_step(delta, None, x, x0, 0.0, e)
+        return x
+
+    def step_universal(self, x, a, e, group=None):
+        """One step of the universal perturbation on δ (``uap.delta``) and the iterate x, both in
+        place (after start_universal); a, e in [-1,1] units. Four stages:
+            1. the gradient chain at x with the per-image Σ|g| (_step_gradient: unscaled g)
+            2. ops.uap_accumulate: acc = Σ_n rint(ĝ_n·2^24), ĝ_n = (−g_n)/mean|g_n|, int64
+            3. ``group``: one all_reduce(acc, SUM) over the job (uap_all_reduce)
+            4. ops.uap_step: δ ← clamp(δ + a·sgn(acc), −e, e); x_n ← clamp(x0_n + δ, −1, 1)
+        Nothing is read back to the host (a gloo group sums through a CPU copy). Every image is
+        normalised by its own mean |g|, so the loss scale cancels; a non-finite ĝ marks its image
+        in self.nonfinite and contributes 0."""
+        b = self._uap_buffers(x.shape)
+        l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
+        g = self._step_gradient(x, l1=l1)
+        ops.uap_accumulate(g, l1, b["acc"], True, nonfinite=self.nonfinite)
+        uap_all_reduce(b["acc"], group)
+        ops.uap_step(b["delta"], b["acc"], x, self.x0, _f32(a), _f32(e))
+        return x
+
+    def run_universal(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None,
+                      group=None):
+        """The universal L∞ perturbation: ONE δ (1,3,S,S), ‖δ‖∞ ≤ e, fitted on all images of the
+        job, with e = 2·eps, a = 2·alpha. δ₀ = 0 (or the random start), then ``steps`` times
+            ĝ_n = (−∇L(x_n)) / mean|∇L(x_n)|;  A = Σ_n rint(ĝ_n·2^24)      (int64, over ALL images)
+            δ ← clamp(δ + a·sgn(A), −e, e);  x_n ← clamp(x0_n + δ, −1, 1)
+        (step_universal). The sum over the images is an integer sum, so δ depends on neither the
+        order of the images, nor the batch split, nor the world size (``group``: one all-reduce
+        per step, the one attack with a collective in its data path). Returns the batch
+        clamp(x0 + δ) (new tensor); δ is kept in self.uap_delta (a clone, on the device). An fp16
+        loss-scale re-run restarts from δ₀."""
+        return self._with_rescale(
+            lambda: self._run_universal(x0, t, steps, eps, alpha, random_start, start_noise,
+                                        group), group)
+
+    def _run_universal(self, x0, t, steps, eps, alpha, random_start, start_noise, group):
+        e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
+        x = self.start_universal(x0, t, eps, random_start, start_noise)
+        for _ in range(steps):
+            self.step_universal(x, a, e, group)
+        self.uap_delta = self._uap_buffers(x0.shape)["delta"].clone()
+        return x.clone()
+
     # ---- Auto-PGD ------------------------------------------------------------------------------
     def _apgd_buffers(self, shape, steps=None):
         """The workspace buffers ``apgd.*`` of a batch of ``shape`` (``steps``: of the attack that
@@ -1097,8 +1254,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
            di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
-           vt_samples=None, vt_beta=1.5, vt_first_image=0, spsa_samples=None, spsa_delta=0.01,
-           spsa_first_image=0, apgd=False):
+           vt_samples=None, vt_beta=1.5, vt_first_image=0, universal=False, spsa_samples=None,
+           spsa_delta=0.01, spsa_first_image=0, apgd=False):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -1200,6 +1357,27 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     vt_first_image  the global index of imgs[0] (default 0), an integer ≥ 0: image n draws the
             noise of image vt_first_image + n, so attacking a slice of a batch with its offset
             gives the rows of the whole batch (``dist.attack_distributed`` passes the shard's).
+    universal  False (default): one perturbation per image. True, with norm='linf' only: ONE
+            perturbation δ (1,3,S,S), ‖δ‖∞ ≤ e, fitted on the whole batch, that steers the
+            fusion of any of its images (and, it is hoped, of held-out ones:
+            ``apply_universal(imgs, delta)``) towards the target. δ₀ = 0, or clamp(e·u, −e, e)
+            with random_start, u ONE draw ``make_start_noise((1,3,S,S), seed, "linf")`` or a
+            ``start_noise`` of that shape. Per step, with x_n = clamp(x0_n + δ, −1, 1):
+                      ĝ_n = (−∇L(x_n)) / mean|∇L(x_n)|             (the MIFGSM normalisation)
+                      A   = Σ_n round_half_even(ĝ_n·2^24)          (int64, over ALL images)
+                      δ   ← clamp(δ + a·sign(A), −e, e);  x_n ← clamp(x0_n + δ, −1, 1)
+            Every image is normalised by its own mean |∇L|, so no image dominates and the fp16
+            loss scale cancels. This is the one attack whose images are not independent: the sum
+            over them is taken in 2^-24 fixed point on exact integer sums (fused HIP kernels),
+            which are associative, so the result is bit-reproducible and depends on neither the
+            order of the images, nor the batch split, nor the world size — a float sum could not
+            promise that. The range needs images × 3·S² < 2^37, counted over the whole job
+            (``check_universal_count``). An image whose gradient is entirely zero or non-finite
+            raises FloatingPointError (fp16: after the loss-scale re-runs, which restart from
+            δ₀). It does not combine with momentum, nesterov, ti_kernel, di_prob / di_schedule,
+            si_scales, vt_samples, spsa_samples or apgd. Returns the batch clamp(x0 + δ); with
+            return_info, info["universal"] holds ``delta`` (1,3,S,S, on the input's device) and
+            ``linf`` = max|δ| in [-1,1] units.
     spsa_samples  None (default): white-box, every rule above reads ∇L. An integer q in 1 … 256
             (SPSA_MAX_SAMPLES), with norm='linf' or 'l2': SPSA, the score-based BLACK-BOX attack
             (Spall 1992; Uesato et al. 2018; torchattacks SPSA's estimator). The attacker sees
@@ -1256,6 +1434,23 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     """
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}")
+    if not isinstance(universal, (bool, np.bool_)):
+        raise ValueError("universal must be True or False")
+    universal = bool(universal)
+    if universal:
+        if norm != "linf":
+            raise ValueError("universal (one perturbation per batch) is implemented for "
+                             "norm='linf' only")
+        mixed = [name for name, on in (
+            ("momentum", momentum is not None),
+            ("nesterov", not isinstance(nesterov, (bool, np.bool_)) or bool(nesterov)),
+            ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
+            ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
+            ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
+            ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd))) if on]
+        if mixed:
+            raise ValueError(f"universal does not combine with {', '.join(mixed)}: the shared "
+                             "step follows the sign of the summed normalised gradients only")
     if not isinstance(apgd, (bool, np.bool_)):
         raise ValueError("apgd must be True or False")
     apgd = bool(apgd)
@@ -1326,6 +1521,14 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     _check_images(imgs, size, "imgs")
     vt_first_image = _check_vt_first_image(vt_first_image, imgs.shape[0])
     spsa_first_image = _check_spsa_first_image(spsa_first_image, imgs.shape[0])
+    if universal:
+        check_universal_count(imgs.shape[0], 3 * size * size)
+        if imgs.shape[0] < 1:
+            raise ValueError("universal needs at least one image")
+        if random_start and start_noise is not None and (
+                not torch.is_tensor(start_noise) or tuple(start_noise.shape) != (1, 3, size, size)):
+            raise ValueError("universal: start_noise must have the shape (1,3,S,S), one draw for "
+                             "the shared perturbation")
     if target is None:
         target = getattr(net, "default_target", None)
     if target is None:
@@ -1365,13 +1568,16 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     eng = AttackEngine(net.encoder.impl, net.decoder.impl, vgg.impl, loss_scale=loss_scale)
     noise = None
     if random_start:
+        noise_shape = (1,) + tuple(x0.shape[1:]) if universal else tuple(x0.shape)
         if start_noise is None:
-            start_noise = make_start_noise(tuple(x0.shape), seed,
-                                           "l2" if norm == "l2" else "linf")
-        if tuple(start_noise.shape) != tuple(x0.shape):
+            start_noise = make_start_noise(noise_shape, seed, "l2" if norm == "l2" else "linf")
+        if tuple(start_noise.shape) != noise_shape:
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if n_spsa is not None:
+    if universal:
+        adv = eng.run_universal(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
+                                group=group)
+    elif n_spsa is not None:
         adv = eng.run_spsa(x0, t, int(steps), float(eps), float(alpha),
                            float(momentum) if momentum is not None else 0.0, norm, random_start,
                            noise, group=group, spsa_samples=n_spsa, spsa_delta=spsa_delta,
@@ -1409,6 +1615,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     spsa_samples=spsa_samples,
                     spsa_delta=spsa_delta if spsa_samples is not None else None,
                     queries=2 * n_spsa * int(steps) if n_spsa is not None else 0)
+        if universal:
+            delta = eng.uap_delta.to(imgs.device)
+            info["universal"] = dict(delta=delta, linf=float(delta.abs().max()))
         if apgd:
             info["apgd"] = eng.apgd_info()
         return adv, info
@@ -1419,7 +1628,8 @@ def fgsm(net, imgs, eps, **kw):
     """FGSM = one PGD step with α = ε and no random start. Every other keyword is forwarded
     unchanged (nesterov's look-ahead is a no-op at the only step, where the momentum is 0; so is
     vt_samples, whose variance term is 0 there: plain FGSM; ``spsa_samples=q`` is the one-step
-    black-box form, the sign of the SPSA estimate). ``apgd=True`` is rejected: one step
+    black-box form, the sign of the SPSA estimate; ``universal=True`` is the one-step universal
+    perturbation, δ = e·sign of the summed normalised gradients). ``apgd=True`` is rejected: one step
     of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM."""
     if kw.get("apgd"):
         raise ValueError("fgsm() takes no apgd: one step of Auto-PGD is not FGSM; call "

@@ -563,6 +563,38 @@ int mia_spsa_accumulate_norms(float* acc, const float* fp, const float* fm, floa
                               int N, int64_t plane, float s, uint64_t seed, uint32_t image0,
                               uint32_t step, uint32_t sample, int first, float div, int* nonfinite,
                               void* stream);
+/* Universal perturbation (Moosavi-Dezfooli et al. 2017's setting, as an L∞ sign iteration): ONE
+ * fp32 plane δ of `plane` elements, ‖δ‖∞ ≤ e, shared by all images, images in [-1,1]. The images
+ * are not independent here, so the cross-image sum is taken in integers: it is associative, and
+ * neither the order of the images nor the split over calls, blocks or ranks can change a bit.
+ *
+ * The per-image terms into the shared sum, per image n and element j:
+ *   ĝ = (−g) / (l1[n] / plane)              (mia_mi_update's normalisation, the same bits)
+ *   q = (int64) rint(ĝ·2^24)                (the product is exact; rint is round-half-even)
+ *   acc[j] = (first ? 0 : acc[j]) + Σ_n q
+ * g: fp32, N images of `plane` elements; l1: fp32 [N] in device memory (Σ|g_n|, from
+ * mia_grad_assemble_norms); acc: int64 [plane], 8-byte aligned, not read when first ≠ 0; g, l1,
+ * acc and nonfinite distinct. Every image is normalised by its own mean |g|, so no image
+ * dominates, a loss scale cancels, and the range is known: |ĝ| < 2·plane. An element outside that
+ * range (NaN and ±Inf included: an all-zero gradient's 0/0, an overflow) sets nonfinite[n] (NULL
+ * or int[N]) and contributes 0; the other images' terms are untouched. Then |q| ≤ 2^25·plane, and
+ * a sum over n images stays inside int64 for n·plane < 2^37, with n counted over EVERYTHING that
+ * is added into one plane (all calls, all ranks). N in 1 … 65535, plane < 2^31, N·plane < 2^37
+ * (anything else: MIA_EINVAL before any launch). A thread owns 4 consecutive elements and walks
+ * the images; 16-byte loads for plane % 4 == 0 with 16-byte aligned g and acc, scalars otherwise
+ * (the same bits). */
+int mia_uap_accumulate(const float* g, const float* l1, int64_t* acc, int N, int64_t plane,
+                       int first, int* nonfinite, void* stream);
+/* The shared step and its application, one pass:
+ *   δ[j] = clamp(δ[j] + a·sgn(acc[j]), −e, e)     (sgn(0) = 0; in place)
+ *   x[n][j] = clamp(x0[n][j] + δ[j], lo, hi)       for all N images
+ * One fp32 rounding per operation, no contraction: bit-exact vs torch fp32 ops. acc = NULL leaves
+ * δ as it is and applies it only (held-out images). N = 0 with x = x0 = NULL updates δ only (a
+ * rank with an empty shard). delta: fp32 [plane]; acc: int64 [plane], 8-byte aligned; x, x0: fp32,
+ * N images; all distinct. N in 0 … 65535 (N = 0 needs acc), plane < 2^31, a ≥ 0, e > 0, lo ≤ hi
+ * (anything else: MIA_EINVAL before any launch). */
+int mia_uap_step(float* delta, const int64_t* acc, float* x, const float* x0, int N, int64_t plane,
+                 float a, float e, float lo, float hi, void* stream);
 /* Auto-PGD (Croce & Hein 2020; torchattacks APGD.attack_single_run, norm = 'Linf', eot_iter = 1)
  * on cost = −L, images in [-1,1]: three launches per step, all decisions on the device. Per-image
  * state is written by mia_apgd_decide alone (one thread per image) and only read by the other

@@ -329,6 +329,80 @@ int main() {
   expect_error(mia_spsa_accumulate_norms(di_a, sp_f, sp_f + 8, dummy, dummy, 2, 48, 25.f, 5,
                                          0xffffffffu, 0, 0, 1, 1.f, nullptr, nullptr),
                "spsa acc image0 + N > 2^32");
+  // The universal perturbation: null / aliased / overlapping buffers, sizes, the range of the
+  // integer sum, the step and the radius (2 images of 48 floats: g = di_a, x0 = di_b, x = sp_c,
+  // l1 = sp_f; one plane of 48 for delta and acc)
+  float up_d[48];
+  int64_t up_acc[48];
+  expect_error(mia_uap_accumulate(nullptr, sp_f, up_acc, 2, 48, 1, nullptr, nullptr),
+               "uap acc null g");
+  expect_error(mia_uap_accumulate(di_a, nullptr, up_acc, 2, 48, 1, nullptr, nullptr),
+               "uap acc null l1");
+  expect_error(mia_uap_accumulate(di_a, sp_f, nullptr, 2, 48, 1, nullptr, nullptr),
+               "uap acc null acc");
+  expect_error(mia_uap_accumulate(di_a, sp_f, (int64_t*)di_a, 2, 48, 1, nullptr, nullptr),
+               "uap acc is g");
+  expect_error(mia_uap_accumulate(di_a, sp_f, (int64_t*)(di_a + 94), 2, 48, 1, nullptr, nullptr),
+               "uap acc inside g");
+  expect_error(mia_uap_accumulate(di_a, (const float*)(up_acc + 47), up_acc, 2, 48, 1, nullptr,
+                                  nullptr), "uap l1 inside acc");
+  expect_error(mia_uap_accumulate(di_a, di_a + 95, up_acc, 2, 48, 1, nullptr, nullptr),
+               "uap l1 inside g");
+  expect_error(mia_uap_accumulate(di_a, sp_f, up_acc, 2, 48, 1, (int*)sp_f, nullptr),
+               "uap nonfinite is l1");
+  expect_error(mia_uap_accumulate(di_a, sp_f, (int64_t*)((char*)up_acc + 4), 2, 48, 1, nullptr,
+                                  nullptr), "uap acc misaligned");
+  expect_error(mia_uap_accumulate(di_a, sp_f, up_acc, 0, 48, 1, nullptr, nullptr), "uap acc N 0");
+  expect_error(mia_uap_accumulate(di_a, sp_f, up_acc, 1 << 16, 48, 1, nullptr, nullptr),
+               "uap acc N");
+  expect_error(mia_uap_accumulate(di_a, sp_f, up_acc, 2, 0, 1, nullptr, nullptr),
+               "uap acc plane 0");
+  expect_error(mia_uap_accumulate(di_a, sp_f, up_acc, 2, 1LL << 31, 1, nullptr, nullptr),
+               "uap acc plane 2^31");
+  expect_error(mia_uap_accumulate(di_a, sp_f, up_acc, 65, (1LL << 31) - 1, 1, nullptr, nullptr),
+               "uap acc N * plane >= 2^37");
+  expect_error(mia_uap_step(nullptr, up_acc, sp_c, di_b, 2, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step null delta");
+  expect_error(mia_uap_step(up_d, up_acc, nullptr, di_b, 2, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step null x");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, nullptr, 2, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step null x0");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 0, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step N 0 with images");
+  expect_error(mia_uap_step(up_d, nullptr, nullptr, nullptr, 0, 48, 0.01f, 0.06f, -1.f, 1.f,
+                            nullptr), "uap step nothing to do");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, -1, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step N < 0");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 1 << 16, 48, 0.01f, 0.06f, -1.f, 1.f,
+                            nullptr), "uap step N");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 0, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step plane 0");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 1LL << 31, 0.01f, 0.06f, -1.f, 1.f,
+                            nullptr), "uap step plane 2^31");
+  expect_error(mia_uap_step(up_d, (const int64_t*)up_d, sp_c, di_b, 2, 48, 0.01f, 0.06f, -1.f,
+                            1.f, nullptr), "uap step acc is delta");
+  expect_error(mia_uap_step(up_d, (const int64_t*)((char*)up_acc + 4), sp_c, di_b, 2, 48, 0.01f,
+                            0.06f, -1.f, 1.f, nullptr), "uap step acc misaligned");
+  expect_error(mia_uap_step(up_d, up_acc, di_b, di_b, 2, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step x is x0");
+  expect_error(mia_uap_step(up_d, up_acc, di_b + 95, di_b, 2, 48, 0.01f, 0.06f, -1.f, 1.f,
+                            nullptr), "uap step x overlaps x0");
+  expect_error(mia_uap_step(up_d, up_acc, up_d, di_b, 2, 48, 0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step x is delta");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, up_d + 47, 2, 48, 0.01f, 0.06f, -1.f, 1.f,
+                            nullptr), "uap step x0 inside delta");
+  expect_error(mia_uap_step(up_d, up_acc, (float*)up_acc, di_b, 2, 48, 0.01f, 0.06f, -1.f, 1.f,
+                            nullptr), "uap step x is acc");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 48, -0.01f, 0.06f, -1.f, 1.f, nullptr),
+               "uap step a < 0");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 48, nanf(""), 0.06f, -1.f, 1.f, nullptr),
+               "uap step a nan");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 48, 0.01f, 0.f, -1.f, 1.f, nullptr),
+               "uap step e 0");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 48, 0.01f, nanf(""), -1.f, 1.f, nullptr),
+               "uap step e nan");
+  expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 48, 0.01f, 0.06f, 1.f, -1.f, nullptr),
+               "uap step lo > hi");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
