@@ -13,11 +13,11 @@ without a GPU; any compute call without the library or a GPU raises.
 """
 __all__ = ["attack", "fgsm", "build_net", "vgg16", "get_latents", "StyleFusionSimple",
            "interpolation", "partial_adv_fusion_arithmetic", "attack_distributed",
-           "patch_attack", "patch_white_box", "apply_universal"]
+           "patch_attack", "patch_white_box", "apply_universal", "sh_schedule"]
 
 
 def __getattr__(name):
-    if name in ("attack", "fgsm", "AttackEngine", "apply_universal"):
+    if name in ("attack", "fgsm", "AttackEngine", "apply_universal", "sh_schedule"):
         from . import pgd as _a
         return getattr(_a, name)
     if name in ("build_net", "vgg16", "get_latents", "PSPNet", "Decoder", "Encoder", "VGGBase",

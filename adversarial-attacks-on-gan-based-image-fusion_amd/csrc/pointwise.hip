@@ -1716,6 +1716,101 @@ __global__ __launch_bounds__(TPB) void apgd_apply_kernel(float* __restrict__ x,
   }
 }
 
+// ---- SignHunter (Al-Dujaili & O'Reilly 2020): every iterate is a vertex clamp(x0 + e·s) of the
+// ball, s ∈ {−1, +1} stored as int8 (a clamped element of x no longer shows its sign). A query
+// flips s on one contiguous segment [lo, hi) of every image and, in the same pass, flips the
+// previous query's segment [plo, phi) back in the images whose decision (accept[n], written by an
+// EARLIER launch of sh_decide_kernel) rejected it:
+//   m = (plo ≤ j < phi && accept[n] == 0 ? −1 : 1)·(lo ≤ j < hi ? −1 : 1)
+//   j in either range:  s[j] *= m;  x[j] = clamp(x0[j] + e·s[j], lo_v, hi_v)
+// e·s is ±e exactly, so x is one fp32 rounding. The grid covers the groups g0 … g0 + ng − 1 of 4
+// consecutive elements (counted from the image start) that the hull of the two ranges meets; a
+// thread owns one group and masks its lanes: an element outside both ranges is neither loaded nor
+// stored, one inside their union is written exactly once. VEC moves a group that lies wholly
+// inside the union as one 16-byte (x, x0) / 4-byte (s) vector and every other group as guarded
+// scalars, !VEC all of them as scalars: the same bits.
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void sh_flip_kernel(float* __restrict__ x,
+                                                      const float* __restrict__ x0,
+                                                      signed char* __restrict__ s,
+                                                      const int* __restrict__ accept,
+                                                      int64_t plane, int64_t g0, int64_t ng,
+                                                      int64_t plo, int64_t phi, int64_t lo,
+                                                      int64_t hi, float e, float lo_v, float hi_v) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;
+  const bool revert = accept != nullptr && accept[n] == 0;
+  const int64_t base = (int64_t)n * plane;
+  for (int64_t t = blockIdx.x * (int64_t)TPB + threadIdx.x; t < ng; t += (int64_t)gridDim.x * TPB) {
+    const int64_t j0 = (g0 + t) * 4;
+    bool on[4], neg[4];
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t j = j0 + k;
+      const bool ip = j >= plo && j < phi, in = j >= lo && j < hi;
+      on[k] = ip || in;
+      neg[k] = (ip && revert) != in;
+      cnt += on[k] ? 1 : 0;
+    }
+    if (cnt == 0) continue;
+    const int64_t i0 = base + j0;
+    if (VEC && cnt == 4) {
+      float xv[4], x0v[4];
+      ldv<4>(x0 + i0, x0v);
+      const char4 sv = *reinterpret_cast<const char4*>(s + i0);
+      signed char sk[4] = {(signed char)sv.x, (signed char)sv.y, (signed char)sv.z,
+                           (signed char)sv.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (neg[k]) sk[k] = (signed char)-sk[k];
+        const float r = x0v[k] + (sk[k] < 0 ? -e : e);
+        xv[k] = fminf(fmaxf(r, lo_v), hi_v);
+      }
+      *reinterpret_cast<char4*>(s + i0) = make_char4(sk[0], sk[1], sk[2], sk[3]);
+      stv<4>(x + i0, xv);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!on[k]) continue;
+        signed char sk = s[i0 + k];
+        if (neg[k]) sk = (signed char)-sk;
+        const float r = x0[i0 + k] + (sk < 0 ? -e : e);
+        s[i0 + k] = sk;
+        x[i0 + k] = fminf(fmaxf(r, lo_v), hi_v);
+      }
+    }
+  }
+}
+
+// The accept / reject decision of one query, one thread per image, on L = loss[n]:
+//   first (query 0): best = L, accept = 1, n_accept = 0
+//   else:            accept = L < best;  accept: best = L, n_accept += 1
+// A tie, a NaN and ±Inf are rejections; a non-finite L marks its image. hist_loss[n] = L.
+__global__ void sh_decide_kernel(const float* __restrict__ loss, float* __restrict__ best,
+                                 int* __restrict__ accept, int* __restrict__ n_accept,
+                                 float* __restrict__ hist_loss, int N, int first,
+                                 int* __restrict__ nonfinite) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const float L = loss[n];
+  const bool finite = __builtin_isfinite(L);
+  if (!finite && nonfinite) nonfinite[n] = 1;
+  if (first) {
+    best[n] = L;
+    accept[n] = 1;
+    n_accept[n] = 0;
+  } else {
+    const bool acc = finite && L < best[n];
+    if (acc) {
+      best[n] = L;
+      n_accept[n] += 1;
+    }
+    accept[n] = acc ? 1 : 0;
+  }
+  hist_loss[n] = L;
+}
+
 // ---- translation-invariant smoothing (torchattacks TIFGSM): gs = (taps ⊗ taps) ⋆ g per plane,
 // zero padded, with the per-image partial sums of |gs| (quantity 0) and gs² (quantity 1).
 // One block = one TI_T × TI_T output tile of one plane, on a (C·tiles, N) grid: the geometry
@@ -3059,6 +3154,53 @@ extern "C" int mia_apgd_apply(float* x, float* g, float* x_best, float* g_best, 
   if (vec)
     MIA_LAUNCH(apgd_apply_kernel<true>, grid, dim3(TPB), 0, x, g, x_best, g_best, action, plane);
   MIA_LAUNCH(apgd_apply_kernel<false>, grid, dim3(TPB), 0, x, g, x_best, g_best, action, plane);
+}
+
+extern "C" int mia_sh_flip(float* x, const float* x0, int8_t* s, const int* accept, int N,
+                           int64_t plane, int64_t prev_lo, int64_t prev_hi, int64_t lo, int64_t hi,
+                           float e, float lo_v, float hi_v, void* stream) {
+  MIA_CHECK_ARG(x && x0 && s, "null x / x0 / s");
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(0 <= prev_lo && prev_lo <= prev_hi && prev_hi <= plane,
+                "need 0 <= prev_lo <= prev_hi <= plane");
+  MIA_CHECK_ARG(0 <= lo && lo <= hi && hi <= plane, "need 0 <= lo <= hi <= plane");
+  MIA_CHECK_ARG(prev_lo < prev_hi || lo < hi, "both ranges are empty: nothing to do");
+  MIA_CHECK_ARG(__builtin_isfinite(e) && e > 0.f, "e must be finite and > 0");
+  MIA_CHECK_ARG(lo_v <= hi_v, "need lo_v <= hi_v");
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(x, x0, len) && !byte_overlap(x, len * 4, s, len) &&
+                    !byte_overlap(x0, len * 4, s, len) &&
+                    !(accept && (byte_overlap(accept, (int64_t)N * 4, x, len * 4) ||
+                                 byte_overlap(accept, (int64_t)N * 4, x0, len * 4) ||
+                                 byte_overlap(accept, (int64_t)N * 4, s, len))),
+                "x, x0, s and accept must be distinct buffers");
+  // the hull of the non-empty ranges, in groups of 4 elements counted from the image start
+  const bool hp = prev_lo < prev_hi, hn = lo < hi;
+  const int64_t h0 = hp && hn ? (prev_lo < lo ? prev_lo : lo) : hp ? prev_lo : lo;
+  const int64_t h1 = hp && hn ? (prev_hi > hi ? prev_hi : hi) : hp ? prev_hi : hi;
+  const int64_t g0 = h0 / 4, ng = (h1 + 3) / 4 - g0;
+  const bool vec = plane % 4 == 0 && aligned16(x) && aligned16(x0) && ((uintptr_t)s & 3) == 0;
+  const dim3 grid(blocks_for(ng, TPB, 1024), N);
+  if (vec)
+    MIA_LAUNCH(sh_flip_kernel<true>, grid, dim3(TPB), 0, x, x0, (signed char*)s, accept, plane, g0,
+               ng, prev_lo, prev_hi, lo, hi, e, lo_v, hi_v);
+  MIA_LAUNCH(sh_flip_kernel<false>, grid, dim3(TPB), 0, x, x0, (signed char*)s, accept, plane, g0,
+             ng, prev_lo, prev_hi, lo, hi, e, lo_v, hi_v);
+}
+
+extern "C" int mia_sh_decide(const float* loss, float* best, int* accept, int* n_accept,
+                             float* hist_loss, int N, int first, int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(loss && best && accept && n_accept && hist_loss, "null argument");
+  MIA_CHECK_ARG(N > 0 && N <= 65535, "N must be in 1 … 65535");
+  MIA_CHECK_ARG(first == 0 || first == 1, "first must be 0 or 1");
+  // every pair of the arrays, N 4-byte words each
+  const void* b[6] = {loss, best, accept, n_accept, hist_loss, nonfinite};
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      MIA_CHECK_ARG(!b[i] || !b[j] || !byte_overlap(b[i], (int64_t)N * 4, b[j], (int64_t)N * 4),
+                    "loss, best, accept, n_accept, hist_loss and nonfinite must be distinct buffers");
+  MIA_LAUNCH(sh_decide_kernel, dim3((N + 63) / 64), dim3(64), 0, loss, best, accept, n_accept,
+             hist_loss, N, first, nonfinite);
 }
 
 extern "C" int mia_cw_init(const float* x, float* w, int64_t len, void* stream) {

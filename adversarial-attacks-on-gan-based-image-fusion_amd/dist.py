@@ -81,6 +81,10 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
     * Auto-PGD (``apgd=True``) needs nothing more: its step sizes, counters and best iterates
       are per image and live on the shard's device, and its only random state is the start
       noise sliced above, so the output does not depend on the world size.
+    * SignHunter (``sign_hunter=True``) needs nothing more either: it draws no random number,
+      its segments (``pgd.sh_schedule``) depend on the image size alone, and its sign planes,
+      best objectives and decisions are per image on the shard's device, so the output does not
+      depend on the world size.
     * The universal perturbation (``universal=True``) is the one attack whose images are not
       independent, and the one attack with a collective per step: every step all-reduces (SUM)
       the int64 plane of the summed normalised gradients over ``group``

@@ -1008,6 +1008,77 @@ def apgd_apply(x, g, x_best, g_best, action):
     return x
 
 
+def _sh_range(r, plane, name):
+    """A segment (lo, hi) of an image's elements, 0 <= lo <= hi <= plane; None is the empty one."""
+    if r is None:
+        return 0, 0
+    try:
+        lo, hi = r
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be None or a pair (lo, hi)") from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"{name} must hold integers")
+    if not 0 <= lo <= hi <= plane:
+        raise ValueError(f"{name}: need 0 <= lo <= hi <= {plane} (elements per image)")
+    return int(lo), int(hi)
+
+
+def sh_flip(x, x0, s, accept, prev, new, e, lo=-1.0, hi=1.0):
+    """One SignHunter query's change of the iterate (mia_sh_flip): the sign plane s (int8, ±1) is
+    flipped on the segment ``new`` = (lo, hi) of every image and flipped back on ``prev`` in the
+    images with accept[n] == 0 (accept None: no image), and x = clamp(x0 + e·s, lo, hi) is
+    rewritten on the union of the two segments only. x, x0: distinct fp32 batches of one shape; s:
+    int8 of that shape; accept: int32 [N] or None; prev / new: (lo, hi) in elements of one image,
+    or None for an empty segment (not both)."""
+    N, plane = _si_images(x, x0, "x", "x0")
+    _need(s, x.shape, torch.int8, "s")
+    _numel_ok(accept, N, torch.int32, "accept")
+    prev, new = _sh_range(prev, plane, "prev"), _sh_range(new, plane, "new")
+    if prev[0] == prev[1] and new[0] == new[1]:
+        raise ValueError("prev and new are both empty: nothing to do")
+    if isinstance(e, bool) or not isinstance(e, numbers.Real) or not math.isfinite(e) or e <= 0:
+        raise ValueError("e must be a finite number > 0")
+    if not float(lo) <= float(hi):
+        raise ValueError("need lo <= hi")
+    call("mia_sh_flip", ptr(x), ptr(x0), ptr(s), ptr(accept), N, plane, prev[0], prev[1], new[0],
+         new[1], float(e), float(lo), float(hi), stream())
+    return x
+
+
+def sh_decide(loss, best, accept, n_accept, hist_loss, query, nonfinite=None):
+    """The accept / reject decision of SignHunter's query ``query`` on loss[n] (mia_sh_decide).
+    Query 0 initialises best = loss, accept = 1, n_accept = 0; a later query sets accept =
+    loss < best and, where it holds, best = loss and n_accept += 1 (a tie, NaN or ±Inf: rejected;
+    non-finite marks ``nonfinite``). best: fp32 [N]; accept, n_accept: int32 [N]; hist_loss: fp32
+    (rows, N), whose row ``query`` receives the loss."""
+    if loss is None or loss.dim() != 1 or loss.dtype != torch.float32 or loss.numel() == 0:
+        raise ValueError("loss must be a non-empty 1-D fp32 tensor")
+    N = loss.numel()
+    _need(best, (N,), torch.float32, "best")
+    _need(accept, (N,), torch.int32, "accept")
+    _need(n_accept, (N,), torch.int32, "n_accept")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    if isinstance(query, bool) or not isinstance(query, numbers.Integral) or query < 0:
+        raise ValueError("query must be an integer >= 0")
+    if (hist_loss is None or hist_loss.dim() != 2 or hist_loss.dtype != torch.float32
+            or hist_loss.shape[1] != N):
+        raise ValueError("hist_loss must be an fp32 (rows, N) tensor")
+    if not query < hist_loss.shape[0]:
+        raise ValueError(f"hist_loss has no row {query}")
+    _distinct([("loss", loss), ("best", best), ("hist_loss", hist_loss)])
+    _distinct([("accept", accept), ("n_accept", n_accept)])
+    call("mia_sh_decide", ptr(loss), ptr(best), ptr(accept), ptr(n_accept),
+         ptr(hist_loss[int(query)]), N, 1 if query == 0 else 0, ptr(nonfinite), stream())
+    return accept
+
+
+def fill_bytes_(t, value):
+    """Every byte of t ← value (0 … 255), on the stream (mia_memset)."""
+    call("mia_memset", ptr(t), int(value) & 0xFF, t.numel() * t.element_size(), stream())
+    return t
+
+
 def cw_init(x, w):
     _need(w, x.shape, torch.float32, "w")
     call("mia_cw_init", ptr(x), ptr(w), x.numel(), stream())

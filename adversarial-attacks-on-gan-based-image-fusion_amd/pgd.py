@@ -974,6 +974,108 @@ class AttackEngine:
                     best_step=b["state_i"][2].cpu().to(torch.int64),
                     halvings=(eta[1:] < eta[:-1]).sum(dim=0))
 
+    # ---- SignHunter: the deterministic score-based black-box attack ---------------------------
+    def _sh_buffers(self, shape, steps=None):
+        """The workspace buffers ``sh.*`` of a batch of ``shape`` (``steps``: of the attack that
+        start_sign_hunter began): the sign plane ``s`` int8 (N, plane); per image ``best`` and the
+        query's objective ``f`` (fp32), the last decision ``accept`` and the count ``n_accept``
+        (int32); the history ``loss`` (steps + 1, N)."""
+        ws, f32, i32, N = self.ws, torch.float32, torch.int32, shape[0]
+        steps = self.sh_steps if steps is None else steps
+        plane = int(np.prod(shape[1:]))
+        return dict(s=ws.get("sh.s", (N, plane), torch.int8), best=ws.get("sh.best", (N,), f32),
+                    f=ws.get("sh.f", (N,), f32), accept=ws.get("sh.accept", (N,), i32),
+                    n_accept=ws.get("sh.n_accept", (N,), i32),
+                    loss=ws.get("sh.loss", (steps + 1, N), f32))
+
+    def _sh_query(self, x, b, k):
+        """Query k at the iterate x: the objective (forward passes only) and the decision."""
+        self.objective(x, ops.zero_(b["f"]))
+        ops.sh_decide(b["f"], b["best"], b["accept"], b["n_accept"], b["loss"], k,
+                      nonfinite=self.nonfinite)
+
+    def start_sign_hunter(self, x0, t, eps, steps=0):
+        """prepare() and query 0 of a SignHunter attack of ``steps`` flips: s = +1 everywhere
+        (the sign plane prefilled with −1 and flipped whole), x = clamp(x0 + e·s, −1, 1),
+        L_best = L(x), row 0 of the history. Returns the iterate buffer for step_sign_hunter."""
+        self.prepare(x0, t)
+        self.sh_steps = int(steps)
+        self.sh_e = _f32(2.0 * eps)
+        plane = int(np.prod(x0.shape[1:]))
+        self.sh_rows = sh_schedule(self.sh_steps, plane)
+        b = self._sh_buffers(x0.shape)
+        x = self.ws.get("adv", x0.shape, torch.float32)
+        ops.fill_bytes_(b["s"], 0xFF)
+        ops.sh_flip(x, x0, b["s"].view(x0.shape), None, None, (0, plane), self.sh_e)
+        self._sh_query(x, b, 0)
+        return x
+
+    def step_sign_hunter(self, x, k):
+        """Query k (1 … steps) of the attack start_sign_hunter began, on the iterate x in place:
+        one launch flips the signs on row k − 1 of sh_schedule and flips row k − 2 back in the
+        images that rejected query k − 1 (ops.sh_flip, on those two segments only), then the
+        objective at the new vertex and the per-image decision (ops.sh_decide). Nothing is read
+        back to the host."""
+        if not 1 <= k <= self.sh_steps:
+            raise ValueError("query index outside the attack start_sign_hunter began")
+        b = self._sh_buffers(x.shape)
+        prev = self.sh_rows[k - 2] if k >= 2 else None
+        ops.sh_flip(x, self.x0, b["s"].view(x.shape), b["accept"], prev, self.sh_rows[k - 1],
+                    self.sh_e)
+        self._sh_query(x, b, k)
+        return x
+
+    def finish_sign_hunter(self, x):
+        """After the last query: the images that rejected it get their last segment flipped back,
+        so x holds every image's best vertex."""
+        if self.sh_steps >= 1:
+            b = self._sh_buffers(x.shape)
+            ops.sh_flip(x, self.x0, b["s"].view(x.shape), b["accept"], self.sh_rows[-1], None,
+                        self.sh_e)
+        return x
+
+    def run_sign_hunter(self, x0, t, steps, eps, group=None):
+        """SignHunter (Al-Dujaili & O'Reilly 2020), L∞, with e = fp32(2·eps); no alpha, no random
+        numbers. Every iterate is a vertex clamp(x0 + e·s, −1, 1) of the ball, s ∈ {−1, +1} per
+        element (kept as int8: a clamped element loses its sign). Per image independently:
+            query 0:  s = +1;  L_best = L(x)
+            query k = 1 … steps:  flip s on row k − 1 of sh_schedule(steps, 3·S²), evaluate L;
+                                  L < L_best: keep the flip, L_best = L; else flip back
+        (a tie or a NaN is a rejection). Returns every image's best vertex (new tensor);
+        ``steps`` = 0 returns a copy of x0 without a query, else steps + 1 queries per image, one
+        forward pass each (self.sh_queries). The attack reads the objective's value only, so the
+        loss scale plays no part; a non-finite objective marks its image and raises as a
+        non-finite gradient does (_with_rescale). All state lives on the device (workspace
+        buffers ``sh.*``): no per-query host synchronisation. The schedule depends on the image
+        size alone, so reruns are bit-identical and an image's result depends on neither the
+        batch nor the world size."""
+        steps = int(steps)
+        self.sh_queries = steps + 1 if steps > 0 else 0
+        return self._with_rescale(lambda: self._run_sign_hunter(x0, t, steps, eps), group)
+
+    def _run_sign_hunter(self, x0, t, steps, eps):
+        if steps == 0:
+            self.prepare(x0, t)
+            self.sh_steps = 0
+            return x0.clone()
+        x = self.start_sign_hunter(x0, t, eps, steps)
+        for k in range(1, steps + 1):
+            self.step_sign_hunter(x, k)
+        return self.finish_sign_hunter(x).clone()
+
+    def sign_hunter_info(self):
+        """The record of the last SignHunter run, on the host (one sync): ``loss`` (steps + 1, N),
+        the objective of every query; ``best`` [N], the objective of the returned vertex;
+        ``accepted`` [N], the number of flips kept. A run of 0 steps made no query: ``loss`` has
+        no row, ``best`` is NaN and ``accepted`` 0."""
+        N = self.x0.shape[0]
+        if self.sh_steps == 0:
+            return dict(loss=torch.zeros((0, N)), best=torch.full((N,), float("nan")),
+                        accepted=torch.zeros((N,), dtype=torch.int64))
+        b = self._sh_buffers(self.x0.shape)
+        return dict(loss=b["loss"].cpu(), best=b["best"].cpu(),
+                    accepted=b["n_accept"].cpu().to(torch.int64))
+
 
 APGD_RHO = 0.75       # a checkpoint flags an image with at most floor(ρ·k) decreases in k steps
 APGD_MOMENTUM = 0.75  # the weight a of the new step against the previous displacement (i > 0)
@@ -999,6 +1101,30 @@ def apgd_schedule(steps):
             rows.append((i, k, 3 * k // 4))
             counter = 0
             k = max(k - dec, k_min)
+    return rows
+
+
+def sh_schedule(steps, plane):
+    """The segments SignHunter flips, a pure function of (``steps``, ``plane`` = elements per
+    image): a list of ``steps`` rows (lo, hi), row k − 1 being the segment [lo, hi) of query k.
+    Divide and conquer: level h starts at 0 and has the chunk length len = ceil(plane / 2^h); its
+    rows are (i·len, min((i + 1)·len, plane)) for i = 0 … ceil(plane / len) − 1, which tile
+    [0, plane). After the level with len = 1 (every element on its own) h wraps to 0, otherwise
+    h += 1. plane = 192: the lengths 192, 96, 48, 24, 12, 6, 3, 2, 1, a cycle of 415 rows."""
+    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)) or steps < 0:
+        raise ValueError("need integer steps >= 0")
+    if (isinstance(plane, (bool, np.bool_)) or not isinstance(plane, (int, np.integer))
+            or not 1 <= plane < 1 << 31):
+        raise ValueError("plane must be an integer in 1 … 2^31 − 1")
+    steps, plane = int(steps), int(plane)
+    rows, h = [], 0
+    while len(rows) < steps:
+        ln = (plane + (1 << h) - 1) >> h
+        for i in range((plane + ln - 1) // ln):
+            if len(rows) == steps:
+                break
+            rows.append((i * ln, min((i + 1) * ln, plane)))
+        h = 0 if ln == 1 else h + 1
     return rows
 
 
@@ -1254,8 +1380,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
            di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
-           vt_samples=None, vt_beta=1.5, vt_first_image=0, universal=False, spsa_samples=None,
-           spsa_delta=0.01, spsa_first_image=0, apgd=False):
+           vt_samples=None, vt_beta=1.5, vt_first_image=0, sign_hunter=False, universal=False,
+           spsa_samples=None, spsa_delta=0.01, spsa_first_image=0, apgd=False):
     """Craft adversarial images against the GAN fusion pipeline.
 
     net     pSp-like bundle: net.encoder, net.decoder (.size), net.latent_avg, net.opts
@@ -1357,6 +1483,32 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     vt_first_image  the global index of imgs[0] (default 0), an integer ≥ 0: image n draws the
             noise of image vt_first_image + n, so attacking a slice of a batch with its offset
             gives the rows of the whole batch (``dist.attack_distributed`` passes the shard's).
+    sign_hunter  False (default). True, with norm='linf' only: SignHunter (Al-Dujaili & O'Reilly,
+            "Sign Bits Are All You Need for Black-Box Attacks", ICLR 2020), the deterministic
+            score-based BLACK-BOX attack, AttackEngine.run_sign_hunter. The attacker sees the
+            objective's value only, one forward pass per query, and draws no random number.
+            ``alpha`` is not used. Every iterate is a vertex of the ε-ball; with e = fp32(2·eps),
+            s ∈ {−1, +1} per element and flat element index j in NCHW order, per image:
+                      query 0:  s = +1;  x = clamp(x0 + e·s, −1, 1);  L_best = L(x)
+                      query k = 1 … steps:  flip s on [lo, hi) = row k − 1 of
+                                sh_schedule(steps, 3·S²);  x = clamp(x0 + e·s, −1, 1)
+                                L(x) < L_best: keep the flip, L_best = L(x);  else flip back
+            A tie or a NaN is a rejection. ``sh_schedule`` is divide and conquer: the whole
+            plane, its halves, quarters, … down to single elements, then again from the whole
+            plane. The result is every image's best vertex; steps + 1 queries per image
+            (info["queries"]; steps = 0 returns a copy of imgs without a query). The signs are
+            kept in an int8 plane — a clamped element of x no longer shows its sign — and one
+            fused HIP kernel per query flips the new segment and, in the images that rejected
+            the previous query, flips that one back, touching those two segments only; a
+            one-thread-per-image kernel takes the decision. Nothing is read back to the host
+            inside the loop. The attack is deterministic by construction: reruns are
+            bit-identical and an image's result depends on neither the batch nor the world size.
+            The clean image is not a candidate (L(x0) is never queried). A non-finite objective
+            raises FloatingPointError. It does not combine with momentum, nesterov, ti_kernel,
+            di_prob / di_schedule, si_scales, vt_samples, spsa_samples, apgd, universal or
+            random_start. With return_info, info["sign_hunter"] holds ``loss`` (steps + 1, N:
+            the objective of every query), ``best`` (N,) and ``accepted`` (N,), the number of
+            flips kept, as host tensors (False without the keyword).
     universal  False (default): one perturbation per image. True, with norm='linf' only: ONE
             perturbation δ (1,3,S,S), ‖δ‖∞ ≤ e, fitted on the whole batch, that steers the
             fusion of any of its images (and, it is hoped, of held-out ones:
@@ -1434,6 +1586,25 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     """
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}")
+    if not isinstance(sign_hunter, (bool, np.bool_)):
+        raise ValueError("sign_hunter must be True or False")
+    sign_hunter = bool(sign_hunter)
+    if sign_hunter:
+        if norm != "linf":
+            raise ValueError("sign_hunter (SignHunter) is implemented for norm='linf' only")
+        mixed = [name for name, on in (
+            ("momentum", momentum is not None),
+            ("nesterov", not isinstance(nesterov, (bool, np.bool_)) or bool(nesterov)),
+            ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
+            ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
+            ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
+            ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd)),
+            ("universal", not isinstance(universal, (bool, np.bool_)) or bool(universal)),
+            ("random_start", bool(random_start))) if on]
+        if mixed:
+            raise ValueError(f"sign_hunter does not combine with {', '.join(mixed)}: it reads "
+                             "the objective's value only and every iterate is a vertex of the "
+                             "ball, reached by sign flips from s = +1")
     if not isinstance(universal, (bool, np.bool_)):
         raise ValueError("universal must be True or False")
     universal = bool(universal)
@@ -1447,7 +1618,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
             ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
-            ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd))) if on]
+            ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd)),
+            ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"universal does not combine with {', '.join(mixed)}: the shared "
                              "step follows the sign of the summed normalised gradients only")
@@ -1463,7 +1635,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("momentum", momentum is not None), ("nesterov", not isinstance(nesterov, (bool, np.bool_)) or bool(nesterov)),
             ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
-            ("vt_samples", vt_samples is not None)) if on]
+            ("vt_samples", vt_samples is not None), ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"apgd (Auto-PGD) does not combine with {', '.join(mixed)}: it has "
                              "its own momentum and step-size rule")
@@ -1508,7 +1680,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("nesterov", nesterov), ("ti_kernel", ti_kernel is not None),
             ("di_prob", di_prob is not None), ("di_schedule", di_schedule is not None),
             ("si_scales", si_scales is not None), ("vt_samples", vt_samples is not None),
-            ("apgd", apgd)) if on]
+            ("apgd", apgd), ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"spsa_samples (SPSA) does not combine with {', '.join(mixed)}: "
                              "they transform or reuse a true gradient, SPSA reads the "
@@ -1548,7 +1720,10 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             di = check_di_schedule(di_schedule, steps, size)
         else:
             di = make_di_schedule(int(steps), size, di_resize_rate, di_prob, seed)
-    if norm in ("linf", "l2") and not (eps is not None and eps > 0 and alpha > 0):
+    if sign_hunter:
+        if not (eps is not None and eps > 0):
+            raise ValueError("sign_hunter needs eps > 0")
+    elif norm in ("linf", "l2") and not (eps is not None and eps > 0 and alpha > 0):
         raise ValueError("PGD needs eps > 0 and alpha > 0")
     if norm in ("adam", "l2_cw") and not lr > 0:
         raise ValueError("lr must be > 0")
@@ -1574,7 +1749,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         if tuple(start_noise.shape) != noise_shape:
             raise ValueError("start_noise must have the shape of imgs")
         noise = start_noise.to(dev, torch.float32).contiguous()
-    if universal:
+    if sign_hunter:
+        adv = eng.run_sign_hunter(x0, t, int(steps), float(eps), group=group)
+    elif universal:
         adv = eng.run_universal(x0, t, int(steps), float(eps), float(alpha), random_start, noise,
                                 group=group)
     elif n_spsa is not None:
@@ -1614,7 +1791,11 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     vt_beta=vt_beta if vt_samples is not None else None,
                     spsa_samples=spsa_samples,
                     spsa_delta=spsa_delta if spsa_samples is not None else None,
-                    queries=2 * n_spsa * int(steps) if n_spsa is not None else 0)
+                    sign_hunter=False,
+                    queries=(2 * n_spsa * int(steps) if n_spsa is not None
+                             else eng.sh_queries if sign_hunter else 0))
+        if sign_hunter:
+            info["sign_hunter"] = eng.sign_hunter_info()
         if universal:
             delta = eng.uap_delta.to(imgs.device)
             info["universal"] = dict(delta=delta, linf=float(delta.abs().max()))
@@ -1630,7 +1811,11 @@ def fgsm(net, imgs, eps, **kw):
     vt_samples, whose variance term is 0 there: plain FGSM; ``spsa_samples=q`` is the one-step
     black-box form, the sign of the SPSA estimate; ``universal=True`` is the one-step universal
     perturbation, δ = e·sign of the summed normalised gradients). ``apgd=True`` is rejected: one step
-    of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM."""
+    of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM.
+    ``sign_hunter=True`` is rejected too: SignHunter follows no gradient."""
+    if kw.get("sign_hunter"):
+        raise ValueError("fgsm() takes no sign_hunter: SignHunter follows no gradient, one flip "
+                         "of it is not FGSM; call attack(..., steps=1, sign_hunter=True) for that")
     if kw.get("apgd"):
         raise ValueError("fgsm() takes no apgd: one step of Auto-PGD is not FGSM; call "
                          "attack(..., steps=1, apgd=True) for that")

@@ -648,6 +648,42 @@ int mia_apgd_decide(const float* loss, float* fstate, int* istate, int* action, 
  * copies, vector or scalar as above. */
 int mia_apgd_apply(float* x, float* g, float* x_best, float* g_best, const int* action, int N,
                    int64_t plane, void* stream);
+/* SignHunter (Al-Dujaili & O'Reilly, "Sign Bits Are All You Need for Black-Box Attacks", ICLR
+ * 2020), L∞, images in [-1,1]: every iterate is a vertex x = clamp(x0 + e·s, lo_v, hi_v) of the
+ * ball, s ∈ {−1, +1} per element, kept as int8 because a clamped element of x no longer shows its
+ * sign. Two launches per query besides the objective, all decisions on the device.
+ *
+ * One query's change of the iterate, per image n and element j of its plane (NCHW order): flip s
+ * on the new segment [lo, hi) and flip the previous query's segment [prev_lo, prev_hi) back where
+ * that query was rejected,
+ *   m = (prev_lo ≤ j < prev_hi and accept[n] == 0 ? −1 : 1) · (lo ≤ j < hi ? −1 : 1)
+ *   j in either range:  s[j] *= m;  x[j] = clamp(x0[j] + e·s[j], lo_v, hi_v)
+ * e·s is exact, so x is one fp32 rounding, no contraction: bit-exact vs torch fp32 ops. The ranges
+ * may overlap; either may be empty, not both. accept (int32 [N], written by an EARLIER launch of
+ * mia_sh_decide, so the kernel never reads what it writes) may be NULL: no revert. Every element
+ * of the union is written exactly once; an element outside both ranges is neither loaded nor
+ * stored. The launch covers the hull of the two ranges, not the plane. The start (s = +1,
+ * x = clamp(x0 + e)) is s prefilled with −1 and one flip of the whole plane without accept.
+ * x, x0: fp32, s: int8, N images of `plane` elements, distinct buffers. A thread owns the 4
+ * consecutive elements of a 4-aligned group counted from the image start and masks the lanes
+ * outside the ranges, whether it moves a whole group as one 16-byte (x, x0) / 4-byte (s) vector
+ * (plane % 4 == 0, x and x0 16-byte and s 4-byte aligned) or as scalars: the same bits; an image's
+ * result does not depend on the other images of the call. N in 1 … 65535, plane in 1 … 2^31 − 1,
+ * 0 ≤ prev_lo ≤ prev_hi ≤ plane, 0 ≤ lo ≤ hi ≤ plane, e finite and > 0, lo_v ≤ hi_v (anything
+ * else: MIA_EINVAL before any launch). */
+int mia_sh_flip(float* x, const float* x0, int8_t* s, const int* accept, int N, int64_t plane,
+                int64_t prev_lo, int64_t prev_hi, int64_t lo, int64_t hi, float e, float lo_v,
+                float hi_v, void* stream);
+/* The accept / reject decision of one SignHunter query, one thread per image n, on L = loss[n]
+ * (the objective at the iterate the last flip produced):
+ *   first ≠ 0 (query 0):  best = L; accept = 1; n_accept = 0
+ *   first = 0:            accept = L < best;  on accept: best = L, n_accept += 1
+ * A tie, a NaN and ±Inf are rejections, and a non-finite L sets nonfinite[n] (NULL or int[N]).
+ * hist_loss[n] = L (the caller passes row `query` of its (steps + 1, N) history). loss, best,
+ * hist_loss: fp32 [N]; accept, n_accept: int32 [N]; device memory, all distinct; N in 1 … 65535,
+ * first in {0, 1} (anything else: MIA_EINVAL before any launch). */
+int mia_sh_decide(const float* loss, float* best, int* accept, int* n_accept, float* hist_loss,
+                  int N, int first, int* nonfinite, void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);

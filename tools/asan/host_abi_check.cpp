@@ -403,6 +403,96 @@ int main() {
                "uap step e nan");
   expect_error(mia_uap_step(up_d, up_acc, sp_c, di_b, 2, 48, 0.01f, 0.06f, 1.f, -1.f, nullptr),
                "uap step lo > hi");
+  // SignHunter: null / aliased / overlapping buffers, sizes, the two ranges, the radius and the
+  // bounds (2 images of 48 elements: x = sp_c, x0 = di_b, s = sh_s, accept = sh_i; the decision's
+  // arrays of 2 words each: loss = sp_f, best = sp_f + 2, hist = sp_f + 4, accept = sh_i,
+  // n_accept = sh_i + 2, nonfinite = sh_i + 4)
+  int8_t sh_s[96];
+  int sh_i[8];
+  expect_error(mia_sh_flip(nullptr, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip null x");
+  expect_error(mia_sh_flip(sp_c, nullptr, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip null x0");
+  expect_error(mia_sh_flip(sp_c, di_b, nullptr, nullptr, 2, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip null s");
+  expect_error(mia_sh_flip(sp_c, sp_c, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip x0 is x");
+  expect_error(mia_sh_flip(sp_c, sp_c + 95, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip x0 overlaps x");
+  expect_error(mia_sh_flip(sp_c, di_b, (int8_t*)sp_c + 383, sh_i, 2, 48, 0, 24, 24, 48, 0.06f,
+                           -1.f, 1.f, nullptr), "sh flip s at x's last byte");
+  expect_error(mia_sh_flip(sp_c, (const float*)(sh_s + 95), sh_s, sh_i, 2, 48, 0, 24, 24, 48,
+                           0.06f, -1.f, 1.f, nullptr), "sh flip x0 at s's last byte");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, (const int*)(sp_c + 95), 2, 48, 0, 24, 24, 48, 0.06f,
+                           -1.f, 1.f, nullptr), "sh flip accept inside x");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, (const int*)(sh_s + 92), 2, 48, 0, 24, 24, 48, 0.06f,
+                           -1.f, 1.f, nullptr), "sh flip accept inside s");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 0, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip N 0");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 1 << 16, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip N");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 0, 0, 0, 0, 0, 0.06f, -1.f, 1.f, nullptr),
+               "sh flip plane 0");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 1LL << 31, 0, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip plane 2^31");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, -1, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip prev_lo < 0");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 25, 24, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip prev_lo > prev_hi");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 49, 24, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip prev_hi > plane");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, -2, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip lo < 0");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 30, 29, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip lo > hi");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 49, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip hi > plane");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 7, 7, 48, 48, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip both ranges empty");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, nullptr, 2, 48, 0, 0, 0, 0, 0.06f, -1.f, 1.f,
+                           nullptr), "sh flip both ranges empty, no accept");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.f, -1.f, 1.f, nullptr),
+               "sh flip e 0");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, -0.06f, -1.f, 1.f,
+                           nullptr), "sh flip e < 0");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, INFINITY, -1.f, 1.f,
+                           nullptr), "sh flip e inf");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, nanf(""), -1.f, 1.f,
+                           nullptr), "sh flip e nan");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.06f, 1.f, -1.f,
+                           nullptr), "sh flip lo_v > hi_v");
+  expect_error(mia_sh_flip(sp_c, di_b, sh_s, sh_i, 2, 48, 0, 24, 24, 48, 0.06f, nanf(""), 1.f,
+                           nullptr), "sh flip lo_v nan");
+  expect_error(mia_sh_decide(nullptr, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, 0, sh_i + 4, nullptr),
+               "sh decide null loss");
+  expect_error(mia_sh_decide(sp_f, nullptr, sh_i, sh_i + 2, sp_f + 4, 2, 0, sh_i + 4, nullptr),
+               "sh decide null best");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, nullptr, sh_i + 2, sp_f + 4, 2, 0, nullptr, nullptr),
+               "sh decide null accept");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, nullptr, sp_f + 4, 2, 0, sh_i + 4, nullptr),
+               "sh decide null n_accept");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, nullptr, 2, 1, sh_i + 4, nullptr),
+               "sh decide null hist");
+  expect_error(mia_sh_decide(sp_f, sp_f, sh_i, sh_i + 2, sp_f + 4, 2, 0, sh_i + 4, nullptr),
+               "sh decide best is loss");
+  expect_error(mia_sh_decide(sp_f, sp_f + 1, sh_i, sh_i + 2, sp_f + 4, 2, 0, sh_i + 4, nullptr),
+               "sh decide best overlaps loss");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 1, sp_f + 4, 2, 0, sh_i + 4, nullptr),
+               "sh decide n_accept overlaps accept");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 3, 2, 0, sh_i + 4, nullptr),
+               "sh decide hist overlaps best");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, 0, sh_i + 3, nullptr),
+               "sh decide nonfinite overlaps n_accept");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, 0, (int*)sp_f, nullptr),
+               "sh decide nonfinite is loss");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 0, 0, sh_i + 4, nullptr),
+               "sh decide N 0");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 1 << 16, 0, sh_i + 4,
+                             nullptr), "sh decide N");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, 2, sh_i + 4, nullptr),
+               "sh decide first 2");
+  expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, -1, sh_i + 4, nullptr),
+               "sh decide first < 0");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
