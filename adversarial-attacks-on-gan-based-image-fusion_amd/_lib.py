@@ -166,6 +166,8 @@ SIGNATURES = {
     "mia_sh_flip": (c_int, [P, P, P, P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
                             c_float, c_float, c_float, P]),
     "mia_sh_decide": (c_int, [P, P, P, P, P, c_int, c_int, P, P]),
+    "mia_pi_update": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float,
+                              c_float, c_float, c_float, c_float, c_float, P, P]),
     "mia_cw_init": (c_int, [P, P, c_int64, P]),
     "mia_cw_tanh": (c_int, [P, P, c_int64, P]),
     "mia_cw_grad": (c_int, [P, P, P, P, c_int64, c_float, c_float, P]),

@@ -1993,6 +1993,198 @@ __global__ __launch_bounds__(TPB) void ti_smooth_norms_kernel(
   block_slot_store<2>(s1, s2, part);
 }
 
+// ---- the patch-wise attack (Gao et al., "Patch-wise Attack for Fooling Deep Neural Network",
+// ECCV 2020; PI-FGSM): the MIFGSM step amplified to ab = β·a, with the part of the accumulated
+// noise A that overflows the ε-ball handed to each pixel's neighbours instead of clipped away.
+// Per plane and pixel, one fp32 rounding per line, no contraction:
+//   ĝ  = (−g) / (l1[n] / plane);  m' = ĝ + μ·m;  s = sign(m')      (mi_update_kernel's, same bits)
+//   A' = A + ab·s;  C = sign(A')·max(|A'| − e, 0)                  (the cut noise, 0 in the ball)
+//   S  = Σ_{dy = −r … r} Σ_{dx = −r … r, (dy, dx) ≠ (0, 0)} C[y + dy, x + dx]
+//        (additions from 0, dy outer and dx inner, both ascending; zero outside the plane)
+//   p  = gm·sign(S);  A ← A' + p
+//   u  = x + ab·s;  v = u + p;  x ← clamp(x0 + clamp(v − x0, −e, e), lo, hi);  m ← m'
+// Only sign(S) is used, so the uniform project kernel's weight 1/(K² − 1) drops out and S is a
+// chain of plain additions in a fixed order: its value depends on the plane and the position
+// only, never on the tile layout or the batch.
+// One block = one TI_T × TI_T tile of one plane on a (C·tiles, N) grid, as ti_smooth_norms_kernel;
+// a thread owns a 4 × 4 patch (4 adjacent columns of 4 rows). Phase 1 computes m', A' and C of
+// the patch (kept in registers) and C of the halo ring — r rows above / below, rl = r rounded up
+// to 4 columns left / right, so that a 16-byte vector is whole — into LDS; an element outside the
+// plane is never read and its C is 0. Phase 2 walks the K + 3 LDS rows under the patch once, each
+// as whole 16-byte slots, and adds row j to the window row dy = j − o of output row o. m and A are
+// read from m_in / A_in and written to m_out / A_out: a block's halo reads its neighbours' OLD
+// state while they write the new one. x is in place (only the thread's own elements are read).
+// VEC (W % 4 == 0, 16-byte aligned bases) moves the 4 columns as one vector, the scalar form the
+// same elements of the same thread one by one: the same bits.
+constexpr int PI_MAXK = 15;  // largest project kernel
+
+template <int K>
+struct PiGeom {
+  static constexpr int r = K >> 1;
+  static constexpr int rl = (r + 3) & ~3;
+  static constexpr int HA = TI_T + 2 * r;
+  static constexpr int WA = TI_T + 2 * rl;
+  static constexpr int SA = WA + 4;  // rows stay 16-byte aligned; rows 8 apart are 32 banks apart
+  static constexpr int floats = HA * SA;
+};
+
+__device__ __forceinline__ float pi_sign(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+// m' (mm), A' (ap) and the cut noise C (returned) of one element; bad |= a non-finite ĝ
+__device__ __forceinline__ float pi_cut(float g, float m, float A, float mean, float mu, float ab,
+                                        float e, float& mm, float& ap, bool& bad) {
+#pragma clang fp contract(off)
+  const float gh = (-g) / mean;
+  bad |= !__builtin_isfinite(gh);
+  const float dec = mu * m;
+  mm = gh + dec;
+  const float st = ab * pi_sign(mm);
+  ap = A + st;
+  const float over = fmaxf(fabsf(ap) - e, 0.f);
+  return ap > 0.f ? over : (ap < 0.f ? -over : 0.f);
+}
+
+template <int K, bool VEC>
+__global__ __launch_bounds__(TPB) void pi_update_kernel(
+    float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ g,
+    const float* __restrict__ l1, const float* __restrict__ m_in, float* __restrict__ m_out,
+    const float* __restrict__ A_in, float* __restrict__ A_out, int C, int H, int W, int tiles_x,
+    int tiles_y, float mu, float ab, float gm, float e, float lo, float hi,
+    int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  typedef PiGeom<K> Q;
+  constexpr int r = Q::r, rl = Q::rl, SA = Q::SA, NC = Q::WA / 4;
+  __shared__ __attribute__((aligned(16))) float cut[Q::floats];
+  const int t = threadIdx.x, n = blockIdx.y;
+  const int tiles = tiles_x * tiles_y;
+  const int c = blockIdx.x / tiles, tile = blockIdx.x - c * tiles;
+  const int ty0 = (tile / tiles_x) * TI_T, tx0 = (tile % tiles_x) * TI_T;
+  const int64_t hw = (int64_t)H * W;
+  const int64_t pbase = ((int64_t)n * C + c) * hw;
+  const float mean = l1[n] / (float)((int64_t)C * hw);
+
+  // phase 1, the thread's own patch: rows ty0 + y0 + o, columns gx … gx + 3, cnt[o] of them inside
+  const int x4 = (t & 15) * 4, y0 = (t >> 4) * 4;
+  const int gx = tx0 + x4;
+  float mm[4][4], ap[4][4];
+  int cnt[4];
+  bool bad = false;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    const int gy = ty0 + y0 + o;
+    cnt[o] = gy < H && gx < W ? (W - gx < 4 ? W - gx : 4) : 0;
+    f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+    if (cnt[o] > 0) {
+      const int64_t i0 = pbase + (int64_t)gy * W + gx;
+      float gg[4], mv[4], av[4];
+      ld4<VEC>(g + i0, cnt[o], gg);
+      ld4<VEC>(m_in + i0, cnt[o], mv);
+      ld4<VEC>(A_in + i0, cnt[o], av);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < cnt[o]) cv[k] = pi_cut(gg[k], mv[k], av[k], mean, mu, ab, e, mm[o][k], ap[o][k], bad);
+    }
+    *(f32x4*)(cut + (r + y0 + o) * SA + rl + x4) = cv;
+  }
+  if (bad && nonfinite) nonfinite[n] = 1;
+
+  // phase 1, the halo ring in 4-column slots: the r rows above and below over the whole width,
+  // then the rl / 4 slots left and right of each of the TI_T rows
+  {
+    constexpr int NTB = 2 * r * NC, NSV = rl / 2, NRING = NTB + TI_T * NSV;
+    for (int i = t; i < NRING; i += TPB) {
+      int row, col4;
+      if (i < NTB) {
+        row = i / NC;
+        col4 = i - row * NC;
+        if (row >= r) row += TI_T;
+      } else {
+        const int j = i - NTB, rr = j / NSV, cs = j - rr * NSV;
+        row = r + rr;
+        col4 = cs < rl / 4 ? cs : cs + TI_T / 4;
+      }
+      const int hy = ty0 - r + row, hx = tx0 - rl + 4 * col4;
+      const int hc = hy >= 0 && hy < H && hx >= 0 && hx < W ? (W - hx < 4 ? W - hx : 4) : 0;
+      f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+      if (hc > 0) {
+        const int64_t i0 = pbase + (int64_t)hy * W + hx;
+        float gg[4], mv[4], av[4];
+        ld4<VEC>(g + i0, hc, gg);
+        ld4<VEC>(m_in + i0, hc, mv);
+        ld4<VEC>(A_in + i0, hc, av);
+        bool unused = false;
+        float mh, ah;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k < hc) cv[k] = pi_cut(gg[k], mv[k], av[k], mean, mu, ab, e, mh, ah, unused);
+      }
+      *(f32x4*)(cut + row * SA + 4 * col4) = cv;
+    }
+  }
+  __syncthreads();
+
+  // phase 2: LDS row y0 + j lies under window row dy = j − o of the patch's output row o
+  float S[4][4];
+#pragma unroll
+  for (int o = 0; o < 4; ++o)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) S[o][k] = 0.f;
+  const float* __restrict__ src = cut + y0 * SA + x4;
+#pragma unroll 1
+  for (int j = 0; j < K + 3; ++j) {
+    float w[4 + 2 * rl];
+#pragma unroll
+    for (int q = 0; q < 1 + rl / 2; ++q) {
+      const f32x4 v = *(const f32x4*)(src + j * SA + 4 * q);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[4 * q + k] = v[k];
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      const int dy = j - o;
+      if (dy < 0 || dy >= K) continue;
+      if (dy == r) {
+#pragma unroll
+        for (int dx = 0; dx < K; ++dx)
+          if (dx != r)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) S[o][k] += w[rl - r + k + dx];
+      } else {
+#pragma unroll
+        for (int dx = 0; dx < K; ++dx)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) S[o][k] += w[rl - r + k + dx];
+      }
+    }
+  }
+
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    if (cnt[o] == 0) continue;
+    const int64_t i0 = pbase + (int64_t)(ty0 + y0 + o) * W + gx;
+    float xv[4], x0v[4], mo[4], ao[4];
+    ld4<VEC>(x + i0, cnt[o], xv);
+    ld4<VEC>(x0 + i0, cnt[o], x0v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k >= cnt[o]) continue;
+      const float p = gm * pi_sign(S[o][k]);
+      ao[k] = ap[o][k] + p;
+      mo[k] = mm[o][k];
+      const float st = ab * pi_sign(mm[o][k]);
+      const float u = xv[k] + st;
+      const float v = u + p;
+      float d = v - x0v[k];
+      d = fminf(fmaxf(d, -e), e);
+      const float rr = x0v[k] + d;
+      xv[k] = fminf(fmaxf(rr, lo), hi);
+    }
+    st4<VEC>(x + i0, cnt[o], xv);
+    st4<VEC>(m_out + i0, cnt[o], mo);
+    st4<VEC>(A_out + i0, cnt[o], ao);
+  }
+}
+
 // ---- input diversity (torchattacks DIFGSM / TIFGSM input_diversity at a fixed image size) ------
 // y = D(x): every plane resized bilinearly (align_corners = False) to rnd × rnd and placed at
 // (top, left) of a zero S × S plane; gx = Dᵀ g with the per-image partial sums of |gx| and gx².
@@ -3201,6 +3393,75 @@ extern "C" int mia_sh_decide(const float* loss, float* best, int* accept, int* n
                     "loss, best, accept, n_accept, hist_loss and nonfinite must be distinct buffers");
   MIA_LAUNCH(sh_decide_kernel, dim3((N + 63) / 64), dim3(64), 0, loss, best, accept, n_accept,
              hist_loss, N, first, nonfinite);
+}
+
+template <int K>
+static int pi_launch(bool vec, dim3 grid, hipStream_t st, float* x, const float* x0, const float* g,
+                     const float* l1, const float* m_in, float* m_out, const float* A_in,
+                     float* A_out, int C, int H, int W, int tiles_x, int tiles_y, float mu, float ab,
+                     float gm, float e, float lo, float hi, int* nonfinite) {
+  if (vec)
+    hipLaunchKernelGGL((pi_update_kernel<K, true>), grid, dim3(TPB), 0, st, x, x0, g, l1, m_in,
+                       m_out, A_in, A_out, C, H, W, tiles_x, tiles_y, mu, ab, gm, e, lo, hi,
+                       nonfinite);
+  else
+    hipLaunchKernelGGL((pi_update_kernel<K, false>), grid, dim3(TPB), 0, st, x, x0, g, l1, m_in,
+                       m_out, A_in, A_out, C, H, W, tiles_x, tiles_y, mu, ab, gm, e, lo, hi,
+                       nonfinite);
+  return check_launch("pi_update_kernel");
+}
+
+extern "C" int mia_pi_update(float* x, const float* x0, const float* g, const float* l1,
+                             const float* m_in, float* m_out, const float* A_in, float* A_out,
+                             int N, int C, int H, int W, int K, float mu, float ab, float gm,
+                             float e, float lo, float hi, int* nonfinite, void* stream) {
+  MIA_CHECK_ARG(x && x0 && g && l1 && m_in && m_out && A_in && A_out, "null argument");
+  MIA_CHECK_ARG(K >= 3 && K <= PI_MAXK && (K & 1), "K must be odd, in 3 … 15");
+  MIA_CHECK_ARG(C > 0 && H > 0 && W > 0, "C, H and W must be > 0");
+  const int64_t hw = (int64_t)H * W;  // < 2^62
+  MIA_CHECK_ARG(hw < (1LL << 31), "C·H·W must be below 2^31");
+  const int64_t plane = (int64_t)C * hw;
+  MIA_CHECK_IMAGES(N, plane);
+  MIA_CHECK_ARG(__builtin_isfinite(mu) && mu >= 0.f, "mu must be finite and >= 0");
+  MIA_CHECK_ARG(__builtin_isfinite(ab) && ab >= 0.f && __builtin_isfinite(gm) && gm >= 0.f &&
+                    __builtin_isfinite(e) && e >= 0.f,
+                "ab, gm and e must be finite and >= 0");
+  MIA_CHECK_ARG(lo <= hi, "need lo <= hi");
+  // m and A ping-pong (a block's halo reads what its neighbours would overwrite); no written
+  // buffer may overlap any other
+  const int64_t len = (int64_t)N * plane;
+  MIA_CHECK_ARG(!di_overlap(m_in, m_out, len), "m_in and m_out must be distinct buffers");
+  MIA_CHECK_ARG(!di_overlap(A_in, A_out, len), "A_in and A_out must be distinct buffers");
+  const float* wr[3] = {x, m_out, A_out};
+  const float* rd[7] = {x0, g, m_in, A_in, x, m_out, A_out};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 7; ++j)
+      MIA_CHECK_ARG(j == i + 4 || !di_overlap(wr[i], rd[j], len),
+                    "x, x0, g, m_in, m_out, A_in and A_out must be distinct buffers");
+  MIA_CHECK_ARG(!byte_overlap(l1, (int64_t)N * 4, x, len * 4) &&
+                    !byte_overlap(l1, (int64_t)N * 4, m_out, len * 4) &&
+                    !byte_overlap(l1, (int64_t)N * 4, A_out, len * 4),
+                "l1 must not overlap x, m_out or A_out");
+  const bool vec = W % 4 == 0 && aligned16(x) && aligned16(x0) && aligned16(g) &&
+                   aligned16(m_in) && aligned16(m_out) && aligned16(A_in) && aligned16(A_out);
+  const int tiles_x = (W + TI_T - 1) / TI_T, tiles_y = (H + TI_T - 1) / TI_T;
+  const dim3 grid(C * tiles_x * tiles_y, N);  // ≤ plane < 2^31 blocks per row
+  const hipStream_t st = (hipStream_t)stream;
+#define MIA_PI_CASE(k)                                                                          \
+  case k:                                                                                       \
+    return pi_launch<k>(vec, grid, st, x, x0, g, l1, m_in, m_out, A_in, A_out, C, H, W, tiles_x, \
+                        tiles_y, mu, ab, gm, e, lo, hi, nonfinite)
+  switch (K) {
+    MIA_PI_CASE(3);
+    MIA_PI_CASE(5);
+    MIA_PI_CASE(7);
+    MIA_PI_CASE(9);
+    MIA_PI_CASE(11);
+    MIA_PI_CASE(13);
+    MIA_PI_CASE(15);
+  }
+#undef MIA_PI_CASE
+  return set_error("mia_pi_update: unsupported K");
 }
 
 extern "C" int mia_cw_init(const float* x, float* w, int64_t len, void* stream) {

@@ -85,6 +85,11 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       its segments (``pgd.sh_schedule``) depend on the image size alone, and its sign planes,
       best objectives and decisions are per image on the shard's device, so the output does not
       depend on the world size.
+    * The patch-wise attack (``pi_amplification=β``) needs nothing more: its momentum and
+      accumulated-noise planes are per image on the shard's device, its window sum runs in a
+      fixed order inside one plane, and its only random state is what the composed keywords
+      bring (the start noise, the DI schedule and the VT noise, handled above), so an image's
+      result depends on neither the batch nor the world size.
     * The universal perturbation (``universal=True``) is the one attack whose images are not
       independent, and the one attack with a collective per step: every step all-reduces (SUM)
       the int64 plane of the summed normalised gradients over ``group``

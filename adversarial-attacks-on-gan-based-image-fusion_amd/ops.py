@@ -1073,6 +1073,43 @@ def sh_decide(loss, best, accept, n_accept, hist_loss, query, nonfinite=None):
     return accept
 
 
+PI_MAX_KERNEL = 15  # mia_pi_update
+
+
+def pi_update(x, x0, g, l1, m_in, m_out, A_in, A_out, mu, ab, gm, e, kernel, lo=-1.0, hi=1.0,
+              nonfinite=None):
+    """The patch-wise attack's step (PI-FGSM, mia_pi_update), per plane of x (N,C,H,W):
+    m' = (−g)/(l1[n]/plane) + mu·m_in; s = sign(m'); A' = A_in + ab·s;
+    Cut = sign(A')·max(|A'| − e, 0); S = the sum of Cut over the kernel × kernel window without
+    its centre (zero padded; dy outer, dx inner, ascending); p = gm·sign(S); A_out = A' + p;
+    x ← clamp(x0 + clamp(x + ab·s + p − x0, −e, e), lo, hi); m_out = m'.
+    x, x0, g, m_in, m_out, A_in, A_out: distinct fp32 (N,C,H,W) tensors (m and A ping-pong: the
+    caller swaps in and out every step); l1: fp32 [N]; kernel odd in 3 … 15; mu, ab, gm, e finite
+    and >= 0. Returns x."""
+    if x is None or x.dim() != 4 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError("x must be a non-empty fp32 (N,C,H,W) tensor")
+    N, C, H, W = x.shape
+    bufs = [("x", x), ("x0", x0), ("g", g), ("m_in", m_in), ("m_out", m_out), ("A_in", A_in),
+            ("A_out", A_out)]
+    for nm, b in bufs[1:]:
+        _need(b, x.shape, torch.float32, nm)
+    _distinct(bufs)
+    _need(l1, (N,), torch.float32, "l1")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    if (isinstance(kernel, bool) or not isinstance(kernel, numbers.Integral)
+            or kernel % 2 == 0 or not 3 <= kernel <= PI_MAX_KERNEL):
+        raise ValueError(f"kernel must be an odd integer in 3 … {PI_MAX_KERNEL}")
+    for v, nm in ((mu, "mu"), (ab, "ab"), (gm, "gm"), (e, "e")):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{nm} must be a finite number >= 0")
+    if not float(lo) <= float(hi):
+        raise ValueError("need lo <= hi")
+    call("mia_pi_update", ptr(x), ptr(x0), ptr(g), ptr(l1), ptr(m_in), ptr(m_out), ptr(A_in),
+         ptr(A_out), N, C, H, W, int(kernel), float(mu), float(ab), float(gm), float(e), float(lo),
+         float(hi), ptr(nonfinite), stream())
+    return x
+
+
 def fill_bytes_(t, value):
     """Every byte of t ← value (0 … 255), on the stream (mia_memset)."""
     call("mia_memset", ptr(t), int(value) & 0xFF, t.numel() * t.element_size(), stream())

@@ -630,6 +630,16 @@ class AttackEngine:
         last): the variance-tuned step (torchattacks VMIFGSM, _vt_grad_norms) on the variance
         buffer ws "vt.v", with the neighbour noise of step index ``vt.step``; None is the step
         without it. The update rule is the same in every case."""
+        g, l1 = self._mi_gradient(x, m, momentum, a, ti_taps, di, nesterov, si_scales, vt)
+        ops.mi_update(x, self.x0, g, l1, m, _f32(momentum), _f32(a), _f32(e),
+                      nonfinite=self.nonfinite)
+        return x
+
+    def _mi_gradient(self, x, m, momentum, a, ti_taps, di, nesterov, si_scales, vt):
+        """What the momentum family's update kernels read: the step's gradient (_step_gradient or,
+        with ``vt``, _vt_grad_norms; at the look-ahead point x + c·m with ``nesterov``, c =
+        momentum·a rounded once to fp32) and its per-image Σ|·| in the zeroed norm.sums[0].
+        Returns (g, l1)."""
         l1 = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))[0]
         di = _di_row(di)
         # No kernel reads c without the look-ahead buffer; the variance-tuned step then passes 0
@@ -640,8 +650,21 @@ class AttackEngine:
             g = self._step_gradient(x, look, c, si_scales, di, ti_taps, l1)
         else:
             g = self._vt_grad_norms(x, look, c, si_scales, di, ti_taps, l1, vt)
-        ops.mi_update(x, self.x0, g, l1, m, _f32(momentum), _f32(a), _f32(e),
-                      nonfinite=self.nonfinite)
+        return g, l1
+
+    def step_pi(self, x, m, A, momentum, e, pi, ti_taps=None, di=None, nesterov=False,
+                si_scales=1, vt=None):
+        """One patch-wise step (PI-FGSM, Gao et al. 2020) on x in place: step_mi's gradient, every
+        option of it included, then ops.pi_update in place of ops.mi_update. ``pi`` is a PiStep
+        (ab = the amplified step β·a, gm = the project step γ·ab, both fp32 and in [-1,1] units,
+        and the project kernel's edge). ``m`` and ``A`` are (in, out) PAIRS of distinct buffers,
+        the momentum and the accumulated amplified noise: the kernel reads the first and writes
+        the second of each, because a tile's halo reads its neighbours' old state while they
+        write the new one; the caller swaps the pair after every step. The Nesterov look-ahead
+        reads m[0] with c = momentum·ab, the step this rule really takes."""
+        g, l1 = self._mi_gradient(x, m[0], momentum, pi.ab, ti_taps, di, nesterov, si_scales, vt)
+        ops.pi_update(x, self.x0, g, l1, m[0], m[1], A[0], A[1], _f32(momentum), pi.ab, pi.gm,
+                      _f32(e), pi.kernel, nonfinite=self.nonfinite)
         return x
 
     def run_l2(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None,
@@ -696,6 +719,14 @@ class AttackEngine:
         function of (vt_seed, vt_first_image + n, k, i, element): a loss-scale re-run starts from
         v = 0 and replays the same noise, and an image's result does not depend on the batch. The
         last step draws no neighbours."""
+        return self._with_rescale(self._mi_runner(
+            x0, t, steps, eps, alpha, momentum, random_start, start_noise, ti_taps, di, nesterov,
+            si_scales, vt_samples, vt_beta, vt_seed, vt_first_image), group)
+
+    def _mi_runner(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise, ti_taps, di,
+                   nesterov, si_scales, vt_samples, vt_beta, vt_seed, vt_first_image, pi=None):
+        """run_mi's / run_pi's arguments checked and moved to the device once, before any re-run:
+        the closure _with_rescale runs."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         rows = _di_rows(di, steps, self.size)
         n_si = _check_si_scales(si_scales)
@@ -703,23 +734,58 @@ class AttackEngine:
         if vt_samples is not None:
             vt = (_check_vt_samples(vt_samples), _check_vt_beta(vt_beta),
                   int(vt_seed) % (1 << 64), _check_vt_first_image(vt_first_image, x0.shape[0]))
-        return self._with_rescale(
-            lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                                 taps, rows, bool(nesterov), n_si, vt), group)
+        return lambda: self._run_mi(x0, t, steps, eps, alpha, momentum, random_start, start_noise,
+                                    taps, rows, bool(nesterov), n_si, vt, pi)
+
+    def run_pi(self, x0, t, steps, eps, alpha, pi_amplification=10.0, pi_kernel=3, pi_project=1.0,
+               momentum=0.0, random_start=False, start_noise=None, group=None, ti_taps=None,
+               di=None, nesterov=False, si_scales=1, vt_samples=None, vt_beta=1.5, vt_seed=0,
+               vt_first_image=0):
+        """The patch-wise attack (Gao, Zhang et al., "Patch-wise Attack for Fooling Deep Neural
+        Network", ECCV 2020; PI-FGSM), L∞, descending L. It changes run_mi's update, not its
+        gradient: the step is amplified to ab = fp32(fp32(β)·a), β = ``pi_amplification``, and the
+        part of the accumulated noise A that overflows the ε-ball is redistributed to each pixel's
+        K × K neighbours (K = ``pi_kernel``, odd in 3 … 15) with the project step gm =
+        fp32(fp32(γ)·ab), γ = ``pi_project``, instead of being clipped away. Per step, image,
+        plane and pixel, with e = 2·eps, a = 2·alpha, m = 0 and A = 0 at the start:
+            ĝ = (−g)/mean|g|;  m ← ĝ + μ·m;  s = sign(m);  A' = A + ab·s
+            C = sign(A')·max(|A'| − e, 0);  S = Σ_{window without its centre} C;  p = gm·sign(S)
+            A ← A' + p;  x ← clamp(x0 + clamp(x + ab·s + p − x0, −e, e), −1, 1)
+        (one fused HIP kernel, ops.pi_update; S is a chain of fp32 additions in a fixed order, zero
+        padded, see include/miattack.h). g is run_mi's gradient with every option of it:
+        ``ti_taps``, ``di``, ``si_scales``, ``vt_*`` and ``nesterov``, whose look-ahead is
+        x + μ·ab·m. m and A ping-pong between two workspace buffers each (mi.m / mi.m1, pi.a0 /
+        pi.a1), swapped every step. A random start and an fp16 loss-scale re-run begin from
+        A = 0. There is no host read-back in the loop. γ = 0 gives run_mi with a = ab; β = 1 with
+        steps·alpha ≤ eps gives run_mi, both bit for bit."""
+        pi = PiStep(*pi_steps(alpha, pi_amplification, pi_project), _check_pi_kernel(pi_kernel))
+        return self._with_rescale(self._mi_runner(
+            x0, t, steps, eps, alpha, momentum, random_start, start_noise, ti_taps, di, nesterov,
+            si_scales, vt_samples, vt_beta, vt_seed, vt_first_image, pi), group)
 
     def _run_mi(self, x0, t, steps, eps, alpha, momentum, random_start, start_noise,
-                ti_taps=None, di=None, nesterov=False, si_scales=1, vt=None):
+                ti_taps=None, di=None, nesterov=False, si_scales=1, vt=None, pi=None):
         e, a = _f32(2.0 * eps), _f32(2.0 * alpha)
+        f32 = torch.float32
         x = self._start(x0, t, e, random_start, start_noise)
-        m = ops.zero_(self.ws.get("mi.m", x0.shape, torch.float32))
+        m = ops.zero_(self.ws.get("mi.m", x0.shape, f32))
         if vt is not None:
             n_vt, beta, key, image0 = vt
             r = _f32(np.float32(beta) * np.float32(e))
-            ops.zero_(self.ws.get("vt.v", x0.shape, torch.float32))
+            ops.zero_(self.ws.get("vt.v", x0.shape, f32))
+        if pi is not None:  # the state ping-pongs: step k reads buffer k % 2 and writes the other
+            ms = (m, self.ws.get("mi.m1", x0.shape, f32))
+            As = (ops.zero_(self.ws.get("pi.a0", x0.shape, f32)),
+                  self.ws.get("pi.a1", x0.shape, f32))
         for k in range(steps):
             step_vt = None if vt is None else VtStep(n_vt, r, key, image0, k, k == steps - 1)
-            self.step_mi(x, m, momentum, a, e, ti_taps, None if di is None else di[k], nesterov,
-                         si_scales, step_vt)
+            row = None if di is None else di[k]
+            if pi is None:
+                self.step_mi(x, m, momentum, a, e, ti_taps, row, nesterov, si_scales, step_vt)
+            else:
+                i, o = k % 2, (k + 1) % 2
+                self.step_pi(x, (ms[i], ms[o]), (As[i], As[o]), momentum, e, pi, ti_taps, row,
+                             nesterov, si_scales, step_vt)
         return x.clone()
 
     # ---- SPSA: the score-based black-box attack ------------------------------------------------
@@ -1189,6 +1255,54 @@ def _check_vt_first_image(vt_first_image, n):
     return int(vt_first_image)
 
 
+PI_MAX_KERNEL = ops.PI_MAX_KERNEL  # mia_pi_update's largest project kernel
+# One patch-wise step (step_pi's ``pi``): the amplified step ab = fp32(fp32(β)·a), the project step
+# gm = fp32(fp32(γ)·ab), both in [-1,1] units, and the project kernel's edge K.
+PiStep = collections.namedtuple("PiStep", "ab gm kernel")
+
+
+def _check_pi_amplification(pi_amplification):
+    """attack()'s / run_pi's ``pi_amplification`` (the paper's β): a finite number > 0."""
+    if (isinstance(pi_amplification, (bool, np.bool_))
+            or not isinstance(pi_amplification, numbers.Real)
+            or not np.isfinite(float(pi_amplification)) or not float(pi_amplification) > 0):
+        raise ValueError("pi_amplification must be None or a finite number > 0")
+    return float(pi_amplification)
+
+
+def _check_pi_kernel(pi_kernel):
+    """attack()'s / run_pi's ``pi_kernel``: an odd integer in 3 … PI_MAX_KERNEL."""
+    if (isinstance(pi_kernel, (bool, np.bool_)) or not isinstance(pi_kernel, (int, np.integer))
+            or pi_kernel % 2 == 0 or not 3 <= pi_kernel <= PI_MAX_KERNEL):
+        raise ValueError(f"pi_kernel must be an odd integer in 3 … {PI_MAX_KERNEL}")
+    return int(pi_kernel)
+
+
+def _check_pi_project(pi_project):
+    """attack()'s / run_pi's ``pi_project`` (the paper's γ over β·α): a finite number >= 0."""
+    if (isinstance(pi_project, (bool, np.bool_)) or not isinstance(pi_project, numbers.Real)
+            or not np.isfinite(float(pi_project)) or not float(pi_project) >= 0):
+        raise ValueError("pi_project must be a finite number >= 0")
+    return float(pi_project)
+
+
+def pi_steps(alpha, pi_amplification, pi_project=1.0):
+    """(ab, gm) of the patch-wise attack in [-1,1] units, in fp32 arithmetic with one rounding per
+    operation: a = fp32(2·alpha), ab = fp32(fp32(pi_amplification)·a), gm = fp32(fp32(pi_project)·ab).
+    Raises where ab is not a finite number > 0 or gm is not finite."""
+    beta, gamma = _check_pi_amplification(pi_amplification), _check_pi_project(pi_project)
+    with np.errstate(over="ignore"):
+        ab = np.float32(beta) * np.float32(2.0 * float(alpha))
+        gm = np.float32(gamma) * ab
+    if not (np.isfinite(ab) and ab > 0):
+        raise ValueError("pi_amplification: the amplified step fp32(pi_amplification·2·alpha) must "
+                         "be a finite number > 0")
+    if not np.isfinite(gm):
+        raise ValueError("pi_project: the project step fp32(pi_project·pi_amplification·2·alpha) "
+                         "must be finite")
+    return float(ab), float(gm)
+
+
 SPSA_MAX_SAMPLES = 256  # antithetic pairs per step (torchattacks SPSA's default nb_sample is 128)
 # The Philox key of the SPSA directions is (seed + SPSA_SEED_OFFSET) mod 2^64 ("SPSA-ATK" in
 # ASCII): a stream of its own, like VT_SEED_OFFSET and DI_SEED_OFFSET.
@@ -1380,7 +1494,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
            di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
-           vt_samples=None, vt_beta=1.5, vt_first_image=0, sign_hunter=False, universal=False,
+           pi_amplification=None, pi_kernel=3, pi_project=1.0, vt_samples=None, vt_beta=1.5, vt_first_image=0, sign_hunter=False, universal=False,
            spsa_samples=None, spsa_delta=0.01, spsa_first_image=0, apgd=False):
     """Craft adversarial images against the GAN fusion pipeline.
 
@@ -1458,6 +1572,36 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             μ·a is rounded once to fp32). No default μ is guessed: torchattacks' decay defaults
             differ between NIFGSM / SINIFGSM (1.0) and TIFGSM / DIFGSM (0.0). At step 1 m = 0, so
             the look-ahead first acts at step 2 (for fgsm() it is a no-op).
+    pi_amplification  None (default): off. A finite β > 0, with norm='linf' only: the patch-wise
+            attack (Gao, Zhang et al., "Patch-wise Attack for Fooling Deep Neural Network", ECCV
+            2020; PI-FGSM, DI-TI-PI-FGSM together with di_prob and ti_kernel; the paper uses
+            β = 10 against normally trained models), AttackEngine.run_pi. It changes the update,
+            not the gradient: the step is amplified to β·a, and the part of the accumulated noise
+            that overflows the ε-ball is handed to each pixel's neighbours by a uniform project
+            kernel instead of being clipped away. With ab = fp32(fp32(β)·a), gm =
+            fp32(fp32(pi_project)·ab), K = pi_kernel, and per image a momentum buffer m and the
+            accumulated amplified noise A, both 0 at the start (also after a random start and an
+            fp16 loss-scale re-run), per step, plane and pixel:
+                      ĝ = (−g)/mean|g|;  m ← ĝ + μ·m;  s = sign(m);  A' = A + ab·s
+                      C = sign(A')·max(|A'| − e, 0)        (the cut noise; 0 inside the ball)
+                      S = Σ C over the K × K window without its centre, zero padded
+                      p = gm·sign(S);  A ← A' + p
+                      x ← clamp(x0 + clamp(x + ab·s + p − x0, −e, e), −1, 1)
+            one fused HIP kernel per step (momentum=None means μ = 0). Only the sign of S is
+            used, so the paper's kernel weights 1/(K² − 1) drop out and S is a chain of fp32
+            additions in a fixed order (window rows, then columns, ascending): the result is
+            bit-reproducible and an image's result depends on neither the batch nor the world
+            size. The paper's test ‖A'‖∞ ≥ ε is implied by C = 0; the authors' clip of C at 10000
+            is unreachable (|A| ≤ steps·(ab + gm)) and left out. g is whatever the other keywords
+            make it: it composes with momentum, nesterov (whose look-ahead becomes x + μ·ab·m),
+            ti_kernel, di_prob / di_schedule, si_scales, vt_samples and random_start at no extra
+            cost. It does not combine with apgd, universal, sign_hunter or spsa_samples.
+            pi_project = 0 gives the MI attack with alpha replaced by β·alpha, and β = 1 with
+            steps·alpha ≤ eps the MI attack itself, both bit for bit.
+    pi_kernel  the project kernel's edge K (default 3, the paper's), an odd integer in 3 … 15.
+            Needs pi_amplification.
+    pi_project  the paper's project factor γ as a multiple of β·α (default 1.0, the paper's
+            γ = β·α), finite and ≥ 0. Needs pi_amplification.
     vt_samples  None (default): no variance tuning. An integer N in 1 … 32 (VT_MAX_SAMPLES;
             torchattacks VMIFGSM's default N is 5), with norm='linf' only: the variance-tuned
             attack (Wang & He; VNI-FGSM together with nesterov). It takes the MIFGSM rule
@@ -1505,8 +1649,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             bit-identical and an image's result depends on neither the batch nor the world size.
             The clean image is not a candidate (L(x0) is never queried). A non-finite objective
             raises FloatingPointError. It does not combine with momentum, nesterov, ti_kernel,
-            di_prob / di_schedule, si_scales, vt_samples, spsa_samples, apgd, universal or
-            random_start. With return_info, info["sign_hunter"] holds ``loss`` (steps + 1, N:
+            di_prob / di_schedule, si_scales, vt_samples, spsa_samples, pi_amplification, apgd,
+            universal or random_start. With return_info, info["sign_hunter"] holds ``loss`` (steps + 1, N:
             the objective of every query), ``best`` (N,) and ``accepted`` (N,), the number of
             flips kept, as host tensors (False without the keyword).
     universal  False (default): one perturbation per image. True, with norm='linf' only: ONE
@@ -1527,7 +1671,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             (``check_universal_count``). An image whose gradient is entirely zero or non-finite
             raises FloatingPointError (fp16: after the loss-scale re-runs, which restart from
             δ₀). It does not combine with momentum, nesterov, ti_kernel, di_prob / di_schedule,
-            si_scales, vt_samples, spsa_samples or apgd. Returns the batch clamp(x0 + δ); with
+            si_scales, vt_samples, spsa_samples, pi_amplification or apgd. Returns the batch
+            clamp(x0 + δ); with
             return_info, info["universal"] holds ``delta`` (1,3,S,S, on the input's device) and
             ``linf`` = max|δ| in [-1,1] units.
     spsa_samples  None (default): white-box, every rule above reads ∇L. An integer q in 1 … 256
@@ -1548,8 +1693,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             bit-identical, there is no host synchronisation, and an image's result depends on
             neither the batch nor the world size. torchattacks SPSA feeds the same estimate to
             Adam; here it feeds the project's own updates. It does not combine with nesterov,
-            ti_kernel, di_prob / di_schedule, si_scales, vt_samples or apgd: each of those
-            transforms or reuses a true gradient. A non-finite objective raises
+            ti_kernel, di_prob / di_schedule, si_scales, vt_samples, pi_amplification or apgd:
+            each of those transforms or reuses a true gradient, or has an update of its own. A non-finite objective raises
             FloatingPointError; so does, under 'linf', a step whose pairs all return
             L(x⁺) = L(x⁻) exactly (an all-zero estimate, 0/0).
     spsa_delta  the probe radius in [0,1] pixel units (default 0.01, torchattacks' delta), finite
@@ -1576,8 +1721,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             torchattacks: at the first checkpoint its check_oscillation compares step 0 with
             loss_steps[-1], a zero row reached by negative indexing; here step 0 is compared
             with the objective at the starting point, the paper's condition. It does not
-            combine with momentum, nesterov, ti_kernel, di_prob / di_schedule, si_scales or
-            vt_samples. With return_info, info["apgd"] holds ``loss`` and ``step_size``
+            combine with momentum, nesterov, ti_kernel, di_prob / di_schedule, si_scales,
+            vt_samples or pi_amplification. With return_info, info["apgd"] holds ``loss`` and ``step_size``
             (steps + 1, N: the start, then after every step), ``best_step`` (0 = the start,
             i + 1 = step i) and ``halvings`` per image, as host tensors.
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
@@ -1598,6 +1743,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
             ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
+            ("pi_amplification", pi_amplification is not None),
             ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd)),
             ("universal", not isinstance(universal, (bool, np.bool_)) or bool(universal)),
             ("random_start", bool(random_start))) if on]
@@ -1618,6 +1764,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
             ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
+            ("pi_amplification", pi_amplification is not None),
             ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd)),
             ("sign_hunter", sign_hunter)) if on]
         if mixed:
@@ -1635,7 +1782,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("momentum", momentum is not None), ("nesterov", not isinstance(nesterov, (bool, np.bool_)) or bool(nesterov)),
             ("ti_kernel", ti_kernel is not None), ("di_prob", di_prob is not None),
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
-            ("vt_samples", vt_samples is not None), ("sign_hunter", sign_hunter)) if on]
+            ("vt_samples", vt_samples is not None),
+            ("pi_amplification", pi_amplification is not None),
+            ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"apgd (Auto-PGD) does not combine with {', '.join(mixed)}: it has "
                              "its own momentum and step-size rule")
@@ -1680,6 +1829,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("nesterov", nesterov), ("ti_kernel", ti_kernel is not None),
             ("di_prob", di_prob is not None), ("di_schedule", di_schedule is not None),
             ("si_scales", si_scales is not None), ("vt_samples", vt_samples is not None),
+            ("pi_amplification", pi_amplification is not None),
             ("apgd", apgd), ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"spsa_samples (SPSA) does not combine with {', '.join(mixed)}: "
@@ -1687,6 +1837,15 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                              "objective's value only")
     spsa_delta = _check_spsa_delta(spsa_delta)
     _check_spsa_first_image(spsa_first_image, 0)
+    pi_kernel, pi_project = _check_pi_kernel(pi_kernel), _check_pi_project(pi_project)
+    if pi_amplification is None:
+        if pi_kernel != 3 or pi_project != 1.0:
+            raise ValueError("pi_kernel / pi_project need pi_amplification (the patch-wise attack "
+                             "is off without it)")
+    else:
+        _check_pi_amplification(pi_amplification)
+        if norm != "linf":
+            raise ValueError("pi_amplification (PI-FGSM) is implemented for norm='linf' only")
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
@@ -1725,6 +1884,8 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             raise ValueError("sign_hunter needs eps > 0")
     elif norm in ("linf", "l2") and not (eps is not None and eps > 0 and alpha > 0):
         raise ValueError("PGD needs eps > 0 and alpha > 0")
+    if pi_amplification is not None:
+        pi_steps(alpha, pi_amplification, pi_project)  # the fp32 steps are finite, β·a > 0
     if norm in ("adam", "l2_cw") and not lr > 0:
         raise ValueError("lr must be > 0")
     if float(imgs.min()) < -1.0 or float(imgs.max()) > 1.0:
@@ -1762,6 +1923,13 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                            spsa_first_image=spsa_first_image)
     elif apgd:
         adv = eng.run_apgd(x0, t, int(steps), float(eps), random_start, noise, group=group)
+    elif pi_amplification is not None:
+        adv = eng.run_pi(x0, t, int(steps), float(eps), float(alpha), pi_amplification, pi_kernel,
+                         pi_project, float(momentum) if momentum is not None else 0.0,
+                         random_start, noise, group=group, ti_taps=ti_taps, di=di,
+                         nesterov=nesterov, si_scales=n_si, vt_samples=n_vt, vt_beta=vt_beta,
+                         vt_seed=(int(seed) + VT_SEED_OFFSET) % (1 << 64),
+                         vt_first_image=vt_first_image)
     elif norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
                              or n_si > 1 or n_vt is not None):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
@@ -1791,7 +1959,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     vt_beta=vt_beta if vt_samples is not None else None,
                     spsa_samples=spsa_samples,
                     spsa_delta=spsa_delta if spsa_samples is not None else None,
-                    sign_hunter=False,
+                    sign_hunter=False, pi_amplification=pi_amplification,
+                    pi_kernel=pi_kernel if pi_amplification is not None else None,
+                    pi_project=pi_project if pi_amplification is not None else None,
                     queries=(2 * n_spsa * int(steps) if n_spsa is not None
                              else eng.sh_queries if sign_hunter else 0))
         if sign_hunter:
@@ -1812,7 +1982,14 @@ def fgsm(net, imgs, eps, **kw):
     black-box form, the sign of the SPSA estimate; ``universal=True`` is the one-step universal
     perturbation, δ = e·sign of the summed normalised gradients). ``apgd=True`` is rejected: one step
     of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM.
-    ``sign_hunter=True`` is rejected too: SignHunter follows no gradient."""
+    ``sign_hunter=True`` is rejected too: SignHunter follows no gradient.
+    ``pi_amplification=β`` is forwarded, the one-step patch-wise attack: every pixel moves by
+    β·ε·s, s the sign of its gradient, its overflow (β − 1)·ε·s (β > 1) votes in its neighbours'
+    windows, and a pixel receives p = ±pi_project·β·ε by the sign of the votes it gets before the
+    ε-clip. The result is clamp(x0 + clamp(β·ε·s + p, −ε, ε)): FGSM's x0 + ε·s where the
+    neighbours agree with the pixel or pi_project < 1, about x0 itself where they outvote it at
+    pi_project = 1 (the two terms cancel), and x0 − ε·s beyond. β ≤ 1 cuts nothing and gives the
+    step β·ε·s."""
     if kw.get("sign_hunter"):
         raise ValueError("fgsm() takes no sign_hunter: SignHunter follows no gradient, one flip "
                          "of it is not FGSM; call attack(..., steps=1, sign_hunter=True) for that")

@@ -684,6 +684,38 @@ int mia_sh_flip(float* x, const float* x0, int8_t* s, const int* accept, int N, 
  * first in {0, 1} (anything else: MIA_EINVAL before any launch). */
 int mia_sh_decide(const float* loss, float* best, int* accept, int* n_accept, float* hist_loss,
                   int N, int first, int* nonfinite, void* stream);
+/* The patch-wise attack's step (Gao, Zhang et al., "Patch-wise Attack for Fooling Deep Neural
+ * Network", ECCV 2020; PI-FGSM), L∞, one fused launch: the MIFGSM step amplified to ab = β·a, with
+ * the part of the accumulated noise A that overflows the ε-ball redistributed to each pixel's
+ * K × K neighbourhood instead of clipped away. Per image n, plane (n, c) of H × W and pixel, with
+ * r = K / 2:
+ *   ĝ  = (−g) / (l1[n] / (C·H·W));  m' = ĝ + mu·m_in      (mia_mi_update's roundings, same bits)
+ *   s  = sign(m')                                          (−1, 0, +1)
+ *   A' = A_in + ab·s
+ *   Cut = sign(A')·max(|A'| − e, 0)                        (the overflow; 0 inside the ball)
+ *   S  = Σ_{dy = −r … r} Σ_{dx = −r … r, (dy, dx) ≠ (0, 0)} Cut[y + dy, x + dx]
+ *   p  = gm·sign(S);  A_out = A' + p
+ *   u  = x + ab·s;  v = u + p;  d = clamp(v − x0, −e, e);  x = clamp(x0 + d, lo, hi)   (in place)
+ *   m_out = m'
+ * Every line is one fp32 operation with one rounding, no contraction. S is a chain of plain fp32
+ * additions starting from 0, dy outer and dx inner, both ascending; a pixel outside the plane
+ * contributes nothing (zero padding) and is never read, and a window never crosses into another
+ * plane. THE ORDER IS PART OF THE CONTRACT: with it the result equals the torch fp32 CPU ops bit
+ * for bit, reruns are bit-identical, and an image's result depends on neither the tiling nor the
+ * other images of the call. Only the sign of S is used, so the paper's uniform project kernel
+ * (weights 1/(K² − 1), zero centre) needs no weights; its test ‖A'‖∞ ≥ ε is implied by Cut = 0.
+ * m and A are NOT updated in place: a block's halo reads its neighbours' old m and A while they
+ * write the new ones, so the caller passes distinct in / out buffers and swaps them every step
+ * (A = 0 and m = 0 before the first). x, x0, g, m_in, m_out, A_in, A_out: fp32 (N,C,H,W), all
+ * distinct; l1: fp32 [N], Σ|g_n| (the *_norms kernels). K odd in 3 … 15; mu, ab, gm, e finite and
+ * ≥ 0; lo ≤ hi; N in 1 … 65535; C·H·W < 2^31 (anything else: MIA_EINVAL before any launch).
+ * nonfinite (NULL or int[N]) is set for an image with a non-finite ĝ element, as mia_mi_update
+ * does. W % 4 == 0 with 16-byte aligned buffers moves 16-byte vectors, anything else scalars: the
+ * same bits. gm = 0 gives x and m_out of mia_mi_update with a = ab. */
+int mia_pi_update(float* x, const float* x0, const float* g, const float* l1, const float* m_in,
+                  float* m_out, const float* A_in, float* A_out, int N, int C, int H, int W, int K,
+                  float mu, float ab, float gm, float e, float lo, float hi, int* nonfinite,
+                  void* stream);
 /* C&W L2 in tanh space (torchattacks CW, interpolation.py:98-193), images in [-1,1]:
  * w = atanh(x) (x clamped to ±(1 − 2^-20)); adv = tanh(w);
  * g_w = (½(adv − x) + c·scale·g_f)·(1 − adv²) for cost = Σ‖(adv − x)/2‖² + c·Σ f(adv);

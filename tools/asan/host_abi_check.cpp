@@ -493,6 +493,62 @@ int main() {
                "sh decide first 2");
   expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, -1, sh_i + 4, nullptr),
                "sh decide first < 0");
+  // The patch-wise step: null / aliased / overlapping buffers (m and A ping-pong, never in
+  // place), the kernel, the sizes and the scalars (2 images of 3 × 4 × 4 = 48 elements, 96 floats
+  // per buffer: x, x0, g, m_in, m_out, A_in, A_out = pi_b[0 … 6]; l1 = pi_l1)
+  float pi_buf[7 * 96], pi_l1[2];
+  float* pi_b[7];
+  for (int i = 0; i < 7; ++i) pi_b[i] = pi_buf + 96 * i;
+  auto pi = [&](float* x, const float* x0, const float* g, const float* l1, const float* m_in,
+                float* m_out, const float* A_in, float* A_out, int N = 2, int C = 3, int H = 4,
+                int W = 4, int K = 3, float mu = 1.f, float ab = 0.1f, float gm = 0.1f,
+                float e = 0.06f, float lo = -1.f, float hi = 1.f, int* nonfinite = nullptr) {
+    return mia_pi_update(x, x0, g, l1, m_in, m_out, A_in, A_out, N, C, H, W, K, mu, ab, gm, e, lo,
+                         hi, nonfinite, nullptr);
+  };
+  float *px = pi_b[0], *px0 = pi_b[1], *pg = pi_b[2], *pmi = pi_b[3], *pmo = pi_b[4],
+        *pai = pi_b[5], *pao = pi_b[6];
+  expect_error(pi(nullptr, px0, pg, pi_l1, pmi, pmo, pai, pao), "pi null x");
+  expect_error(pi(px, nullptr, pg, pi_l1, pmi, pmo, pai, pao), "pi null x0");
+  expect_error(pi(px, px0, nullptr, pi_l1, pmi, pmo, pai, pao), "pi null g");
+  expect_error(pi(px, px0, pg, nullptr, pmi, pmo, pai, pao), "pi null l1");
+  expect_error(pi(px, px0, pg, pi_l1, nullptr, pmo, pai, pao), "pi null m_in");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, nullptr, pai, pao), "pi null m_out");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, nullptr, pao), "pi null A_in");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, nullptr), "pi null A_out");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmi, pai, pao), "pi m in place");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pai), "pi A in place");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmi + 95, pai, pao), "pi m_out overlaps m_in");
+  expect_error(pi(px, px0, pg, pi_l1, pmo + 95, pmo, pai, pao), "pi m_in overlaps m_out");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pai + 1), "pi A_out overlaps A_in");
+  expect_error(pi(px, px, pg, pi_l1, pmi, pmo, pai, pao), "pi x0 is x");
+  expect_error(pi(px, px0, px + 95, pi_l1, pmi, pmo, pai, pao), "pi g overlaps x");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, px, pai, pao), "pi m_out is x");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pmo), "pi A_out is m_out");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pmo + 95, pao), "pi A_in overlaps m_out");
+  expect_error(pi(px, pao + 95, pg, pi_l1, pmi, pmo, pai, pao), "pi x0 overlaps A_out");
+  expect_error(pi(px, px0, pg, px + 95, pmi, pmo, pai, pao), "pi l1 inside x");
+  expect_error(pi(px, px0, pg, pao, pmi, pmo, pai, pao), "pi l1 is A_out");
+  for (int K : {1, 2, 4, 16, 17, 63, 0, -3})
+    expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, K), "pi K");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 0), "pi N 0");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 1 << 16), "pi N");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 0), "pi C 0");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 0), "pi H 0");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, -4), "pi W < 0");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 1, 1 << 16, 1 << 15), "pi H·W 2^31");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 2, 1 << 15, 1 << 15), "pi plane 2^31");
+  for (float v : {-0.5f, INFINITY, -INFINITY, nanf("")}) {
+    expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, 3, v), "pi mu");
+    expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, 3, 1.f, v), "pi ab");
+    expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, 3, 1.f, 0.1f, v), "pi gm");
+    expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, 3, 1.f, 0.1f, 0.1f, v),
+                 "pi e");
+  }
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, 3, 1.f, 0.1f, 0.1f, 0.06f,
+                  1.f, -1.f), "pi lo > hi");
+  expect_error(pi(px, px0, pg, pi_l1, pmi, pmo, pai, pao, 2, 3, 4, 4, 3, 1.f, 0.1f, 0.1f, 0.06f,
+                  nanf(""), 1.f), "pi lo nan");
   expect_error(mia_reserve_reduction_scratch(-1, nullptr), "scratch negative");
   EXPECT(mia_reserve_reduction_scratch(0, nullptr) == MIA_OK, "scratch zero");
 
