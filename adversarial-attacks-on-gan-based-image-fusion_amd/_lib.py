@@ -75,6 +75,7 @@ class GemmGroup(ctypes.Structure):
 SIGNATURES = {
     "mia_version": (c_int, []),
     "mia_last_error_string": (ctypes.c_char_p, []),
+    "mia_last_conv_path": (ctypes.c_char_p, []),
     "mia_conv_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "mia_reduction_workspace_size": (c_int64, [c_int, c_int, c_int]),
     "mia_reserve_reduction_scratch": (c_int, [c_int64, P]),

@@ -596,6 +596,16 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
   }
 }
 
+// The kernel family the calling thread's last conv launch dispatched to (mia_last_conv_path, for
+// tests that must know which kernel they checked): one thread-local store per launch, of a static
+// string. MIA_CONV_PATH appends the epilogue form of a launcher's EPI template argument:
+// −2 the LDS-staged shared epilogue, −1 the register epilogue with runtime features, ≥ 0 a
+// specialised register epilogue.
+void set_conv_path(const char* name);
+const char* get_conv_path();
+#define MIA_CONV_PATH(family, EPI) \
+  mia::set_conv_path((EPI) == -2 ? family "/lds" : (EPI) == -1 ? family "/regrt" : family "/reg")
+
 // fp32 stride-1 3×3 layers with pre-split weights, operands split once (conv_halo_x6.hip)
 bool conv_halo_x6_eligible(const ConvK& k, int dtype);
 int launch_conv_halo_x6(ConvK& k, hipStream_t st);

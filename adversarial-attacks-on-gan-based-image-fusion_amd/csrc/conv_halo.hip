@@ -464,6 +464,7 @@ __global__ __launch_bounds__(TL::NT, TL::WAVES_PER_SIMD) void conv_halo_kernel(c
 
 template <typename T, typename TL, bool PRO, int EPI>
 static int launch_halo_tile_(ConvK& k, hipStream_t st) {
+  MIA_CONV_PATH("halo", EPI);
   k.nbn = (k.a.Cout + TL::BN - 1) / TL::BN;
   const int patches = k.a.N * (k.a.H / TL::PH) * (k.a.W / TL::PW);
   k.nblk = patches * k.nbn;

@@ -609,6 +609,7 @@ __global__ __launch_bounds__(HaloX6<BN_>::NT, 2) void conv_halo_x6_kernel(const 
 template <int BN_, bool PRO, int EPI, bool EARLY, bool PRIO = false, bool UNR = false,
           int TPS = 1, int STG = 0>
 static int launch_x6_e(ConvK& k, hipStream_t st) {
+  MIA_CONV_PATH("halo_x6", EPI);
   typedef HaloX6<BN_, TPS> TL;
   k.nbn = (k.a.Cout + TL::BN - 1) / TL::BN;
   k.nblk = k.a.N * (k.a.H / TL::PH) * (k.a.W / TL::PW) * k.nbn;
@@ -884,6 +885,7 @@ __global__ __launch_bounds__(HaloX6S::NT, 2) void conv_halo_x6s_kernel(const Con
 
 template <bool PRO, int EPI>
 static int launch_x6s_(ConvK& k, hipStream_t st) {
+  MIA_CONV_PATH("halo_x6", EPI);
   typedef HaloX6S TL;
   k.nbn = (k.a.Cout + TL::BN - 1) / TL::BN;
   k.nblk = k.a.N * (k.a.H / TL::PH) * (k.a.W / TL::PW) * k.nbn;

@@ -338,6 +338,10 @@ __global__ __launch_bounds__(TL::NT, TL::NW == 4 && TL::STAGES <= 3 ? (TL::BM < 
 
 template <typename T, typename TL, bool PRO, bool SMALLC, int EPI = -2, bool X6B = false>
 static int launch_tile(ConvK& k, hipStream_t st) {
+  if (X6B) MIA_CONV_PATH("x6b", EPI);
+  else if (TL::BM == 64) MIA_CONV_PATH("tile64x64", EPI);
+  else if (TL::BN == 64) MIA_CONV_PATH("tile128x64", EPI);
+  else MIA_CONV_PATH("tile128x128", EPI);
   k.nbn = (k.a.Cout + TL::BN - 1) / TL::BN;
   int blk = 0;
   for (int g = 0; g < k.ng; ++g) {
@@ -383,6 +387,10 @@ static int launch_tile(ConvK& k, hipStream_t st) {
 typedef Tile<2, 2, 4, 2, 2> Tile128x64;
 typedef Tile<2, 2, 4, 4, 2> Tile128x128;
 typedef Tile<2, 2, 2, 2, 2> Tile64x64;
+
+static thread_local const char* g_conv_path = "";
+void set_conv_path(const char* name) { g_conv_path = name; }
+const char* get_conv_path() { return g_conv_path; }
 
 // Register epilogue on the 128x128 tile: 2-byte types, one group, identity output placement,
 // every tile inside one image (HWo % 128 == 0), the feature masks of the heavy short-K launches
@@ -765,8 +773,14 @@ extern "C" int mia_upconv_fwd(const void* x, const void* const* w_phase, void* t
     G.bx = px;
     G.m = pixels_clamped(N, G.ho, G.wo);
   }
-  return run_conv(k, dtype, (hipStream_t)stream);
+  const int rc = run_conv(k, dtype, (hipStream_t)stream);
+  // the four sub-pixel phases on the generic tile: this name wins over the tile's own, whether or
+  // not the launch succeeded (as the halo form below keeps its name over its edge groups)
+  set_conv_path("phase_gemm");
+  return rc;
 }
+
+extern "C" const char* mia_last_conv_path(void) { return get_conv_path(); }
 
 extern "C" int mia_upconv_fwd_halo(const void* x, const void* const* w_phase, const void* w_up,
                                    void* t_out, int N, int R, int Cin, int Cout, int act_in,
@@ -786,6 +800,7 @@ extern "C" int mia_upconv_fwd_halo_split(const void* x, const void* const* w_pha
   const int rc = launch_upconv_halo(x, w_up, w_up_split, t_out, N, R, Cin, Cout, act_in, style,
                                     dtype, (hipStream_t)stream);
   if (rc) return rc;
+  const char* const interior = get_conv_path();  // the edge groups below do not name the launch
   // the last row / column of the even phase grids (y = R or x = R): four one-row / one-column
   // groups on the generic kernel; the group's input window starts at R − 1 (pad = 1 − R) and its
   // outputs land at T row / column 2R
@@ -829,7 +844,9 @@ extern "C" int mia_upconv_fwd_halo_split(const void* x, const void* const* w_pha
     }
     G.m = pixels_clamped(N, G.ho, G.wo);
   }
-  return run_conv(k, dtype, (hipStream_t)stream);
+  const int rce = run_conv(k, dtype, (hipStream_t)stream);
+  set_conv_path(interior);
+  return rce;
 }
 
 static int upconv_dgrad_impl(const mia_conv_args& a, const void* w_t, int N, int R, int Cout,

@@ -647,6 +647,7 @@ bool conv_thin32_eligible(const ConvK& k, int dtype) {
 
 template <typename T, bool PRO, int F>
 static int launch_thin32_(ConvK& k, int grid, hipStream_t st) {
+  set_conv_path("thin32/reg");  // always halo_epilogue_f<F>: F is a feature mask, not an EPI form
   // one slot per THIN32_CHUNK-group work item of an image (every slot has its contributor)
   const int64_t gpi = (int64_t)k.a.H * (k.a.W / 16);
   RedQ r;
@@ -699,6 +700,7 @@ bool conv_thin_eligible(const ConvK& k, int dtype) {
 }
 
 int launch_conv_thin(ConvK& k, int dtype, hipStream_t st) {
+  set_conv_path("thin");  // (its own epilogue: bias + activation / accumulate in registers)
   const mia_conv_args& a = k.a;
   const int grid = grid_for((int64_t)a.N * a.H * (a.W / 16));  // ≤ 8 waves per SIMD
   if (dtype == MIA_F32) {  // the fp32 VALU kernels (one pixel per thread / per 16 threads)

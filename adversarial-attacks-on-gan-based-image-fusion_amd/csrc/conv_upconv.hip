@@ -371,6 +371,7 @@ __global__ __launch_bounds__(256, 2) void upconv_halo_kernel(const UpK k) {
 template <typename T, bool PRO, bool DG = false, int BN_ = 64>
 static int launch_upconv_halo(UpK& k, hipStream_t st) {
   typedef HaloUpT<BN_> TL;
+  set_conv_path(DG ? "s2dg_halo" : "upconv_halo");
   k.nbn = k.Cout / TL::BN;
   k.nblk = k.N * (k.R / TL::PH) * (k.R / TL::PW) * k.nbn;
   size_t lds = 2 * (size_t)TL::HBUF + (size_t)TL::STAGES * TL::BSTAGE;
@@ -944,6 +945,7 @@ __global__ __launch_bounds__(DgX6S::NT, 2) void upconv_x6s_kernel(const UpK k) {
 template <bool DG, bool PRO>
 static int launch_upconv_x6s(UpK& k, hipStream_t st) {
   typedef DgX6S TL;
+  set_conv_path(DG ? "s2dg_x6s" : "upconv_x6s");
   k.nbn = k.Cout / TL::BN;
   k.nblk = k.N * (k.R / TL::PH) * (k.R / TL::PW) * k.nbn;
   auto fn = upconv_x6s_kernel<DG, PRO>;
@@ -955,6 +957,7 @@ static int launch_upconv_x6s(UpK& k, hipStream_t st) {
 template <bool DG, bool PRO, bool EARLY, bool PRIO>
 static int launch_upconv_x6_e(UpK& k, hipStream_t st) {
   typedef DgX6 TL;
+  set_conv_path(DG ? "s2dg_x6" : "upconv_x6");
   k.nbn = k.Cout / TL::BN;
   k.nblk = k.N * (k.R / TL::PH) * (k.R / TL::PW) * k.nbn;
   auto fn = upconv_x6_kernel<DG, PRO, EARLY, PRIO>;

@@ -237,6 +237,7 @@ __global__ __launch_bounds__(TL::NT, 1) void conv_wres_kernel(const ConvK k) {
 
 template <typename T, typename TL, int EPI>
 static int launch_wres_(ConvK& k, int grid, size_t lds, hipStream_t st) {
+  MIA_CONV_PATH("wres", EPI);
   auto fn = conv_wres_kernel<T, TL, EPI>;
   if (const int rc = ensure_dyn_lds((const void*)fn, 160 * 1024); rc != MIA_OK) return rc;
   RedQ r;
@@ -606,6 +607,7 @@ bool conv_wres32_eligible(const ConvK& k, int dtype) {
 
 template <typename T, bool PRO, int EPI>
 static int launch_wres32_(ConvK& k, hipStream_t st) {
+  MIA_CONV_PATH("wres32", EPI);
   typedef Wres32Tile TL;
   auto fn = conv_wres32_kernel<T, PRO, EPI>;
   // blocks per CU of this instantiation on the current device (cached per kernel and device),

@@ -443,6 +443,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 template <typename T, int CIN, int EPI, int COUT = 128>
 static int launch_wres128_(ConvK& k, hipStream_t st) {
+  MIA_CONV_PATH("wres128", EPI);
   typedef Wres128Tile<CIN, COUT> TL;
   constexpr bool AUXX = (EPI & (epi::SDOT | epi::MASK | epi::ACC)) != 0;
   constexpr bool DG = (EPI & epi::SDOT) != 0;

@@ -53,6 +53,12 @@ def _numel_ok(t, n, dtype=None, name="tensor"):
         raise ValueError(f"{name}: dtype {t.dtype} != {dtype}")
 
 
+def last_conv_path():
+    """The kernel family this thread's last conv launch dispatched to (mia_last_conv_path), e.g.
+    ``"halo/reg"``, ``"wres128/reg"``, ``"tile128x64/lds"``, ``"upconv_halo"``."""
+    return _lib.load().mia_last_conv_path().decode()
+
+
 def conv_kpad(cin, dtype):
     bk = 32 if dtype == torch.float32 else 64
     return (9 * cin + bk - 1) // bk * bk

@@ -48,6 +48,16 @@ extern "C" {
 
 int mia_version(void);
 const char* mia_last_error_string(void);
+/* The kernel family the calling thread's last conv launch (mia_conv3x3 / mia_conv3x3_wmod /
+ * mia_conv2d* / mia_upconv_* / mia_conv_s2_dgrad_halo*) dispatched to, as a static string ("" before
+ * the first launch): thin, thin32, wres, wres32, wres128, halo, halo_x6, tile128x128, tile128x64,
+ * tile64x64, x6b, upconv_halo, upconv_x6, upconv_x6s, s2dg_halo, s2dg_x6, s2dg_x6s, phase_gemm. Where a family
+ * has more than one epilogue form a suffix names the one chosen: "/reg" a register epilogue
+ * specialised for the launch's feature mask, "/regrt" the register epilogue with runtime features,
+ * "/lds" the LDS-staged shared epilogue (e.g. "halo/reg", "tile128x64/lds"). For tests and tuning
+ * tools that must know which kernel they measured; no launch depends on it.
+ * Replaces: nothing in the reference (cuDNN's algorithm choice is internal). */
+const char* mia_last_conv_path(void);
 
 /* ---- reduction scratch (see Conventions) ----------------------------------------------------
  * Upper bounds of the scratch bytes one call needs:

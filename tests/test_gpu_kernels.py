@@ -1,4 +1,8 @@
-"""Kernel-level parity of libmiattack against plain PyTorch fp32/fp64 references (GPU)."""
+"""Kernel-level parity of libmiattack against plain PyTorch fp32/fp64 references (GPU).
+
+The fp16 / bf16 tolerances here are max-norm allowances; the tight check of the kernels that exist
+only for the 2-byte types is tests/test_gpu_conv_bounds.py (a proven element-wise fp64 bound on
+every output element and every fused sum, with the dispatched kernel asserted by name)."""
 import math
 
 import numpy as np
