@@ -554,14 +554,12 @@ def grad_assemble_norms(x, x0, g_vgg, g_enc, g, l1, l2sq, pf, enc_res, coef_img,
     """grad_assemble plus l1[n] += Σ|g_n| and l2sq[n] += Σ g_n² (either may be None), in one pass
     (mia_grad_assemble_norms)."""
     N, C, S, S2 = x.shape
-    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
     if C != 3 or S != S2:
         raise ValueError("x must be (N,3,S,S)")
     _need(x, x.shape, torch.float32, "x")
     _need(x0, x.shape, torch.float32, "x0")
     _need(g, x.shape, torch.float32, "g")
-    _numel_ok(l1, N, torch.float32, "l1")
-    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    _norm_outputs(N, l1, l2sq, nonfinite)
     if pf < 1 or S % pf:
         raise ValueError("pf must divide S")
     R = S // pf
@@ -575,6 +573,13 @@ def grad_assemble_norms(x, x0, g_vgg, g_enc, g, l1, l2sq, pf, enc_res, coef_img,
          ptr(l2sq), N, S, pf, cpad, enc_res, float(coef_img), float(scale), ptr(nonfinite), dt(T),
          stream())
     return g
+
+
+def _norm_outputs(N, l1, l2sq, nonfinite):
+    """The optional per-image outputs of the *_norms entry points: N values each."""
+    _numel_ok(l1, N, torch.float32, "l1")
+    _numel_ok(l2sq, N, torch.float32, "l2sq")
+    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
 
 
 def _image_rows(x, name="x"):
@@ -637,9 +642,7 @@ def ti_smooth_norms(g, taps, gs, l1, l2sq, nonfinite=None):
     K = taps.numel()
     if K % 2 == 0 or not 1 <= K <= 63:
         raise ValueError("taps must hold an odd number of values, 1 … 63")
-    _numel_ok(l1, N, torch.float32, "l1")
-    _numel_ok(l2sq, N, torch.float32, "l2sq")
-    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    _norm_outputs(N, l1, l2sq, nonfinite)
     call("mia_ti_smooth_norms", ptr(g), ptr(gs), ptr(taps), K, ptr(l1), ptr(l2sq), N, C, H, W,
          ptr(nonfinite), stream())
     return gs
@@ -678,9 +681,7 @@ def di_resize_pad_bwd_norms(g, gx, l1, l2sq, rnd, top, left, nonfinite=None):
     """gx ← Dᵀ g, the adjoint of di_resize_pad, with l1[n] += Σ|gx_n| and l2sq[n] += Σ gx_n²
     (either may be None) (mia_di_resize_pad_bwd_norms). g, gx: distinct fp32 (N,C,S,S)."""
     N, C, S, rnd, top, left = _di_args(g, gx, rnd, top, left, "g", "gx")
-    _numel_ok(l1, N, torch.float32, "l1")
-    _numel_ok(l2sq, N, torch.float32, "l2sq")
-    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    _norm_outputs(N, l1, l2sq, nonfinite)
     call("mia_di_resize_pad_bwd_norms", ptr(g), ptr(gx), ptr(l1), ptr(l2sq), N, C, S, rnd, top,
          left, ptr(nonfinite), stream())
     return gx
@@ -720,8 +721,7 @@ def si_transform(x, m, y, c, s):
         _need(m, x.shape, torch.float32, "m")
         if m.data_ptr() == y.data_ptr():
             raise ValueError("m and y must be distinct buffers")
-    if isinstance(c, bool) or not isinstance(c, numbers.Real) or not math.isfinite(c):
-        raise ValueError("c must be a finite number")
+    c = _finite(c, "c")
     s = _si_scale(s, "s")
     call("mia_si_transform", ptr(x), ptr(m), ptr(y), N, plane, float(c), s, stream())
     return y
@@ -732,13 +732,9 @@ def si_accumulate_norms(g, acc, l1, l2sq, w, first, div=1.0, nonfinite=None):
     l1[n] += Σ|acc_n| and l2sq[n] += Σ acc_n² (either may be None) (mia_si_accumulate_norms).
     g, acc: distinct fp32 batches of one shape."""
     N, plane = _si_images(g, acc, "g", "acc")
-    _numel_ok(l1, N, torch.float32, "l1")
-    _numel_ok(l2sq, N, torch.float32, "l2sq")
-    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    _norm_outputs(N, l1, l2sq, nonfinite)
     w = _si_scale(w, "w")
-    if (isinstance(div, bool) or not isinstance(div, numbers.Real) or not math.isfinite(div)
-            or div < 1):
-        raise ValueError("div must be a finite number >= 1")
+    div = _finite(div, "div", ">= 1")
     call("mia_si_accumulate_norms", ptr(g), ptr(acc), ptr(l1), ptr(l2sq), N, plane, w,
          1 if first else 0, float(div), ptr(nonfinite), stream())
     return acc
@@ -763,18 +759,11 @@ def vt_neighbor(x, m, y, c, r, seed, image0, step, sample):
         _need(m, x.shape, torch.float32, "m")
         if m.data_ptr() == y.data_ptr():
             raise ValueError("m and y must be distinct buffers")
-    if isinstance(c, bool) or not isinstance(c, numbers.Real) or not math.isfinite(c):
-        raise ValueError("c must be a finite number")
-    if isinstance(r, bool) or not isinstance(r, numbers.Real) or not math.isfinite(r) or r < 0:
-        raise ValueError("r must be a finite number >= 0")
-    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 64:
-        raise ValueError("seed must be an integer in 0 … 2^64 − 1")
-    image0, step, sample = (_vt_u32(v, nm) for v, nm in ((image0, "image0"), (step, "step"),
-                                                         (sample, "sample")))
-    if image0 + N > 1 << 32:
-        raise ValueError("image0 + N must be <= 2^32")
-    call("mia_vt_neighbor", ptr(x), ptr(m), ptr(y), N, plane, float(c), float(r), int(seed),
-         image0, step, sample, stream())
+    c = _finite(c, "c")
+    r = _finite(r, "r", ">= 0")
+    seed, image0, step, sample = _philox_counter(N, seed, image0, step, sample)
+    call("mia_vt_neighbor", ptr(x), ptr(m), ptr(y), N, plane, c, r, seed, image0, step, sample,
+         stream())
     return y
 
 
@@ -788,19 +777,15 @@ def vt_combine_norms(g, gv, v, gt, l1, nonfinite=None):
     if gv is not None:
         _need(gv, g.shape, torch.float32, "gv")
         bufs.append(("gv", gv))
-    for i, (na, a) in enumerate(bufs):
-        for nb, b in bufs[i + 1:]:
-            if a.data_ptr() == b.data_ptr():
-                raise ValueError(f"{na} and {nb} must be distinct buffers")
-    _numel_ok(l1, N, torch.float32, "l1")
-    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
+    _distinct(bufs)
+    _norm_outputs(N, l1, None, nonfinite)
     call("mia_vt_combine_norms", ptr(g), ptr(gv), ptr(v), ptr(gt), ptr(l1), N, plane,
          ptr(nonfinite), stream())
     return gt
 
 
-def _spsa_counter(N, seed, image0, step, sample):
-    """The key and counter words of the SPSA directions, checked as vt_neighbor checks its own."""
+def _philox_counter(N, seed, image0, step, sample):
+    """The key and counter words of a counter-based launch (vt_neighbor, the SPSA pair)."""
     if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 64:
         raise ValueError("seed must be an integer in 0 … 2^64 − 1")
     image0, step, sample = (_vt_u32(v, nm) for v, nm in ((image0, "image0"), (step, "step"),
@@ -810,9 +795,11 @@ def _spsa_counter(N, seed, image0, step, sample):
     return int(seed), image0, step, sample
 
 
-def _positive(v, name):
-    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
-        raise ValueError(f"{name} must be a finite number > 0")
+def _finite(v, name, bound=""):
+    """v as a float: a finite real number (no bool) within ``bound`` ("", ">= 0", ">= 1", "> 0")."""
+    ok = not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(v)
+    if not (ok and {"": True, ">= 0": v >= 0, ">= 1": v >= 1, "> 0": v > 0}[bound]):
+        raise ValueError(f"{name} must be a finite number {bound}".rstrip())
     return float(v)
 
 
@@ -825,10 +812,10 @@ def spsa_probe(x, yp, ym, d, seed, image0, step, sample, lo=-1.0, hi=1.0):
     N, plane = _si_images(x, yp, "x", "yp")
     _need(ym, x.shape, torch.float32, "ym")
     _distinct([("x", x), ("yp", yp), ("ym", ym)])
-    d = _positive(d, "d")
+    d = _finite(d, "d", "> 0")
     if not float(lo) <= float(hi):
         raise ValueError("need lo <= hi")
-    seed, image0, step, sample = _spsa_counter(N, seed, image0, step, sample)
+    seed, image0, step, sample = _philox_counter(N, seed, image0, step, sample)
     call("mia_spsa_probe", ptr(x), ptr(yp), ptr(ym), N, plane, d, float(lo), float(hi), seed,
          image0, step, sample, stream())
     return yp, ym
@@ -847,11 +834,9 @@ def spsa_accumulate_norms(acc, fp, fm, l1, l2sq, s, seed, image0, step, sample, 
     _need(fp, (N,), torch.float32, "fp")
     _need(fm, (N,), torch.float32, "fm")
     _distinct([("acc", acc), ("fp", fp), ("fm", fm)])
-    _numel_ok(l1, N, torch.float32, "l1")
-    _numel_ok(l2sq, N, torch.float32, "l2sq")
-    _numel_ok(nonfinite, N, torch.int32, "nonfinite")
-    s, div = _positive(s, "s"), _positive(div, "div")
-    seed, image0, step, sample = _spsa_counter(N, seed, image0, step, sample)
+    _norm_outputs(N, l1, l2sq, nonfinite)
+    s, div = _finite(s, "s", "> 0"), _finite(div, "div", "> 0")
+    seed, image0, step, sample = _philox_counter(N, seed, image0, step, sample)
     call("mia_spsa_accumulate_norms", ptr(acc), ptr(fp), ptr(fm), ptr(l1), ptr(l2sq), N, plane, s,
          seed, image0, step, sample, 1 if first else 0, div, ptr(nonfinite), stream())
     return acc
@@ -917,8 +902,7 @@ def uap_step(delta, acc, x, x0, a, e, lo=-1.0, hi=1.0):
         raise ValueError("nothing to do: no images and no acc")
     _distinct(bufs)
     for v, nm in ((a, "a"), (e, "e")):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
-            raise ValueError(f"{nm} must be a finite number")
+        _finite(v, nm)
     if a < 0 or e <= 0:
         raise ValueError("need a >= 0 and e > 0")
     if not float(lo) <= float(hi):
@@ -952,8 +936,7 @@ def apgd_update(x, x_old, x0, g, eta, a, e, lo=-1.0, hi=1.0, nonfinite=None):
     _numel_ok(nonfinite, N, torch.int32, "nonfinite")
     if isinstance(a, bool) or not isinstance(a, numbers.Real) or not 0.0 < a <= 1.0:
         raise ValueError("a must be a number in (0, 1]")
-    if isinstance(e, bool) or not isinstance(e, numbers.Real) or not math.isfinite(e) or e <= 0:
-        raise ValueError("e must be a finite number > 0")
+    e = _finite(e, "e", "> 0")
     if not float(lo) <= float(hi):
         raise ValueError("need lo <= hi")
     call("mia_apgd_update", ptr(x), ptr(x_old), ptr(x0), ptr(g), ptr(eta), N, plane, float(a),
@@ -1043,8 +1026,7 @@ def sh_flip(x, x0, s, accept, prev, new, e, lo=-1.0, hi=1.0):
     prev, new = _sh_range(prev, plane, "prev"), _sh_range(new, plane, "new")
     if prev[0] == prev[1] and new[0] == new[1]:
         raise ValueError("prev and new are both empty: nothing to do")
-    if isinstance(e, bool) or not isinstance(e, numbers.Real) or not math.isfinite(e) or e <= 0:
-        raise ValueError("e must be a finite number > 0")
+    e = _finite(e, "e", "> 0")
     if not float(lo) <= float(hi):
         raise ValueError("need lo <= hi")
     call("mia_sh_flip", ptr(x), ptr(x0), ptr(s), ptr(accept), N, plane, prev[0], prev[1], new[0],
@@ -1106,8 +1088,7 @@ def pi_update(x, x0, g, l1, m_in, m_out, A_in, A_out, mu, ab, gm, e, kernel, lo=
             or kernel % 2 == 0 or not 3 <= kernel <= PI_MAX_KERNEL):
         raise ValueError(f"kernel must be an odd integer in 3 … {PI_MAX_KERNEL}")
     for v, nm in ((mu, "mu"), (ab, "ab"), (gm, "gm"), (e, "e")):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
-            raise ValueError(f"{nm} must be a finite number >= 0")
+        _finite(v, nm, ">= 0")
     if not float(lo) <= float(hi):
         raise ValueError("need lo <= hi")
     call("mia_pi_update", ptr(x), ptr(x0), ptr(g), ptr(l1), ptr(m_in), ptr(m_out), ptr(A_in),

@@ -30,6 +30,13 @@ static void expect_error(int rc, const char* what) {
   EXPECT(msg != nullptr && std::strlen(msg) > 0, what);
 }
 
+// refused, and with this text in the message
+static void expect_message(int rc, const char* text, const char* what) {
+  EXPECT(rc != MIA_OK, what);
+  const char* msg = mia_last_error_string();
+  EXPECT(msg != nullptr && std::strstr(msg, text) != nullptr, what);
+}
+
 int main() {
   EXPECT(mia_version() > 0, "version");
   // tuning table: every documented switch round-trips; unknown / null names are refused
@@ -493,6 +500,100 @@ int main() {
                "sh decide first 2");
   expect_error(mia_sh_decide(sp_f, sp_f + 2, sh_i, sh_i + 2, sp_f + 4, 2, -1, sh_i + 4, nullptr),
                "sh decide first < 0");
+  // Partial overlaps from each side (b starting inside a, and a starting inside b) of the entry
+  // points whose buffers differ in length or element size, each refused with its own message.
+  // Offsets in floats into one allocation; 2 images of 48 elements; nothing is dereferenced.
+  alignas(16) static float ov[512];
+  {
+    const char* m = "acc, fp and fm must be distinct buffers";
+    auto f = [&](int acc, int fp, int fm) {  // acc 96 floats, fp and fm 2 each
+      return mia_spsa_accumulate_norms(ov + acc, ov + fp, ov + fm, dummy, dummy, 2, 48, 25.f, 5, 0,
+                                       0, 0, 1, 1.f, nullptr, nullptr);
+    };
+    expect_message(f(0, 95, 200), m, "spsa acc: fp starts inside acc");
+    expect_message(f(101, 100, 200), m, "spsa acc: acc starts inside fp");
+    expect_message(f(0, 200, 95), m, "spsa acc: fm starts inside acc");
+    expect_message(f(101, 200, 100), m, "spsa acc: acc starts inside fm");
+    expect_message(f(0, 200, 201), m, "spsa acc: fm starts inside fp");
+    expect_message(f(0, 201, 200), m, "spsa acc: fp starts inside fm");
+  }
+  {
+    const char* m = "the state, action, loss and history arrays must be distinct buffers";
+    auto f = [&](int fstate, int istate) {  // fstate 8 floats, istate 6 ints, the others 2 words
+      return mia_apgd_decide(ov, ov + fstate, (int*)(ov + istate), (int*)(ov + 2), ov + 4, ov + 6, 2,
+                             1, 0, 0, 0.f, nullptr);
+    };
+    expect_message(f(8, 15), m, "apgd decide: istate starts inside fstate");
+    expect_message(f(13, 8), m, "apgd decide: fstate starts inside istate");
+    expect_message(f(7, 20), m, "apgd decide: fstate starts inside hist_eta");
+    expect_message(f(20, 3), m, "apgd decide: istate starts inside action");
+  }
+  {
+    const char* m = "loss, best, accept, n_accept, hist_loss and nonfinite must be distinct buffers";
+    auto f = [&](int loss, int best, int accept, int nonfinite) {  // 2 words each
+      return mia_sh_decide(ov + loss, ov + best, (int*)(ov + accept), (int*)(ov + 20), ov + 30, 2, 0,
+                           nonfinite < 0 ? nullptr : (int*)(ov + nonfinite), nullptr);
+    };
+    expect_message(f(0, 1, 10, 40), m, "sh decide: best starts inside loss");
+    expect_message(f(1, 0, 10, 40), m, "sh decide: loss starts inside best");
+    expect_message(f(0, 4, 10, 11), m, "sh decide: nonfinite starts inside accept");
+    expect_message(f(0, 4, 11, 10), m, "sh decide: accept starts inside nonfinite");
+    expect_message(f(0, 4, 1, -1), m, "sh decide: accept starts inside loss, no nonfinite");
+  }
+  {
+    const char* m = "x, x0, s and accept must be distinct buffers";
+    // x, x0 96 floats, s 96 bytes, accept 2 ints
+    auto f = [&](int x, int x0, int s_bytes, int accept) {
+      return mia_sh_flip(ov + x, ov + x0, (int8_t*)ov + s_bytes,
+                         accept < 0 ? nullptr : (int*)(ov + accept), 2, 48, 0, 24, 24, 48, 0.06f, -1.f, 1.f, nullptr);
+    };
+    expect_message(f(0, 95, 4 * 300, 400), m, "sh flip: x0 starts inside x");
+    expect_message(f(95, 0, 4 * 300, 400), m, "sh flip: x starts inside x0");
+    expect_message(f(0, 100, 4 * 95 + 3, 400), m, "sh flip: s starts inside x");
+    expect_message(f(323, 100, 4 * 300, 400), m, "sh flip: x starts inside s");
+    expect_message(f(0, 100, 4 * 300, 323), m, "sh flip: accept starts inside s");
+    expect_message(f(0, 100, 4 * 300 + 7, 300), m, "sh flip: s starts inside accept");
+    expect_message(f(0, 100, 4 * 300, 195), m, "sh flip: accept starts inside x0");
+    expect_message(f(0, 101, 4 * 300, 100), m, "sh flip: x0 starts inside accept");
+    expect_message(f(0, 100, 4 * 95, -1), m, "sh flip: s starts inside x, no accept");
+  }
+  {
+    const char* m = "g, l1, acc and nonfinite must be distinct buffers";
+    // g 96 floats, l1 2, acc 48 int64, nonfinite 2 ints
+    auto f = [&](int g, int l1, int acc, int nonfinite) {
+      return mia_uap_accumulate(ov + g, ov + l1, (int64_t*)(ov + acc), 2, 48, 1,
+                                nonfinite < 0 ? nullptr : (int*)(ov + nonfinite), nullptr);
+    };
+    expect_message(f(0, 300, 94, -1), m, "uap acc: acc starts inside g");
+    expect_message(f(195, 300, 100, -1), m, "uap acc: g starts inside acc");
+    expect_message(f(0, 195, 100, -1), m, "uap acc: l1 starts inside acc");
+    expect_message(f(0, 99, 100, -1), m, "uap acc: acc starts inside l1");
+    expect_message(f(0, 95, 100, -1), m, "uap acc: l1 starts inside g");
+    expect_message(f(1, 0, 100, -1), m, "uap acc: g starts inside l1");
+    expect_message(f(0, 300, 100, 195), m, "uap acc: nonfinite starts inside acc");
+    expect_message(f(0, 300, 100, 99), m, "uap acc: acc starts inside nonfinite");
+    expect_message(f(0, 300, 100, 301), m, "uap acc: nonfinite starts inside l1");
+    expect_message(f(0, 301, 100, 300), m, "uap acc: l1 starts inside nonfinite");
+  }
+  {
+    const char* m2 = "delta and acc must be distinct";
+    const char* m4 = "delta, acc, x and x0 must be distinct buffers";
+    // delta 48 floats, acc 48 int64, x and x0 96 floats
+    auto f = [&](int delta, int acc, int x, int x0) {
+      return mia_uap_step(ov + delta, (const int64_t*)(ov + acc), ov + x, ov + x0, 2, 48, 0.01f,
+                          0.06f, -1.f, 1.f, nullptr);
+    };
+    expect_message(f(0, 46, 200, 300), m2, "uap step: acc starts inside delta");
+    expect_message(f(195, 100, 200, 300), m2, "uap step: delta starts inside acc");
+    expect_message(f(0, 100, 200, 295), m4, "uap step: x0 starts inside x");
+    expect_message(f(0, 100, 295, 200), m4, "uap step: x starts inside x0");
+    expect_message(f(0, 100, 195, 300), m4, "uap step: x starts inside acc");
+    expect_message(f(0, 294, 200, 400), m4, "uap step: acc starts inside x");
+    expect_message(f(0, 100, 200, 47), m4, "uap step: x0 starts inside delta");
+    expect_message(f(295, 100, 300, 200), m4, "uap step: delta starts inside x0");
+    expect_message(mia_uap_step(ov, (const int64_t*)(ov + 46), nullptr, nullptr, 0, 48, 0.01f, 0.06f,
+                                -1.f, 1.f, nullptr), m2, "uap step: acc starts inside delta, N = 0");
+  }
   // The patch-wise step: null / aliased / overlapping buffers (m and A ping-pong, never in
   // place), the kernel, the sizes and the scalars (2 images of 3 × 4 × 4 = 48 elements, 96 floats
   // per buffer: x, x0, g, m_in, m_out, A_in, A_out = pi_b[0 … 6]; l1 = pi_l1)
