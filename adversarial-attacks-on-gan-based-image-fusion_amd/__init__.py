@@ -13,11 +13,13 @@ without a GPU; any compute call without the library or a GPU raises.
 """
 __all__ = ["attack", "fgsm", "build_net", "vgg16", "get_latents", "StyleFusionSimple",
            "interpolation", "partial_adv_fusion_arithmetic", "attack_distributed",
-           "patch_attack", "patch_white_box", "apply_universal", "sh_schedule"]
+           "patch_attack", "patch_white_box", "apply_universal", "sh_schedule", "jpeg_compress",
+           "jpeg_quant_tables", "jpeg_dct_matrix"]
 
 
 def __getattr__(name):
-    if name in ("attack", "fgsm", "AttackEngine", "apply_universal", "sh_schedule"):
+    if name in ("attack", "fgsm", "AttackEngine", "apply_universal", "sh_schedule",
+                "jpeg_compress", "jpeg_quant_tables", "jpeg_dct_matrix"):
         from . import pgd as _a
         return getattr(_a, name)
     if name in ("build_net", "vgg16", "get_latents", "PSPNet", "Decoder", "Encoder", "VGGBase",

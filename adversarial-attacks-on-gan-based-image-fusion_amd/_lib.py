@@ -147,6 +147,8 @@ SIGNATURES = {
     "mia_di_resize_pad": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "mia_di_resize_pad_bwd_norms": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                             P, P]),
+    "mia_jpeg_roundtrip": (c_int, [P, P, P, c_int, c_int, P]),
+    "mia_jpeg_bwd_norms": (c_int, [P, P, P, P, P, P, c_int, c_int, P, P]),
     "mia_si_transform": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, P]),
     "mia_si_accumulate_norms": (c_int, [P, P, P, P, c_int, c_int64, c_float, c_int, c_float, P,
                                         P]),

@@ -90,6 +90,9 @@ def attack_distributed(net, imgs, eps, steps, *, target, group=None, random_star
       fixed order inside one plane, and its only random state is what the composed keywords
       bring (the start noise, the DI schedule and the VT noise, handled above), so an image's
       result depends on neither the batch nor the world size.
+    * The JPEG-robust attack (``jpeg_quality``, ``jpeg_grad``) needs nothing more: the round trip
+      and its adjoint act per image on 8 × 8 blocks, the quantiser tables depend on the quality
+      alone and nothing is drawn, so the output does not depend on the world size.
     * The universal perturbation (``universal=True``) is the one attack whose images are not
       independent, and the one attack with a collective per step: every step all-reduces (SUM)
       the int64 plane of the summed normalised gradients over ``group``

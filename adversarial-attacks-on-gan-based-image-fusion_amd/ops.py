@@ -687,6 +687,49 @@ def di_resize_pad_bwd_norms(g, gx, l1, l2sq, rnd, top, left, nonfinite=None):
     return gx
 
 
+def _jpeg_args(x, qtab, others):
+    """Shared checks of the JPEG pair: x a non-empty fp32 (N,3,S,S) tensor with S % 8 == 0, qtab
+    the (2,64) fp32 device table of quantiser steps (luminance, chrominance; natural order),
+    ``others`` = (name, tensor) pairs of x's shape, all distinct buffers. Returns (N, S)."""
+    if x is None or x.dim() != 4 or x.dtype != torch.float32 or x.numel() == 0 or x.shape[1] != 3:
+        raise ValueError("x must be a non-empty fp32 (N,3,S,S) tensor")
+    N, _, S, S2 = x.shape
+    if S != S2 or S < 8 or S % 8:
+        raise ValueError("x must have square planes (N,3,S,S) with S a multiple of 8")
+    _need(qtab, (2, 64), torch.float32, "qtab")
+    bufs = [x.data_ptr()]
+    for name, t in others:
+        _need(t, x.shape, torch.float32, name)
+        bufs.append(t.data_ptr())
+    if len(set(bufs)) != len(bufs):
+        raise ValueError("x" + "".join(f", {name}" for name, _ in others)
+                         + " must be distinct buffers")
+    return N, S
+
+
+def jpeg_roundtrip(x, y, qtab):
+    """y ← J(x): what saving x as a baseline 4:4:4 JPEG with the quantiser steps ``qtab`` and
+    loading it again does to it — 8-bit pixels, JFIF YCbCr, the 8 × 8 DCT, quantise / dequantise,
+    the inverse DCT, RGB, 8-bit pixels (mia_jpeg_roundtrip; the order of every fp32 operation is
+    in include/miattack.h). x, y: distinct fp32 (N,3,S,S) in [-1,1], S % 8 == 0; qtab: (2,64)
+    fp32 on the device (pgd.jpeg_quant_tables)."""
+    N, S = _jpeg_args(x, qtab, (("y", y),))
+    call("mia_jpeg_roundtrip", ptr(x), ptr(y), ptr(qtab), N, S, stream())
+    return y
+
+
+def jpeg_bwd_norms(x, g, gx, qtab, l1, l2sq, nonfinite=None):
+    """gx ← J′(x)ᵀ g, the adjoint at x of the round trip whose coefficient rounding is replaced by
+    round(v) + (v − round(v))³ (Shin & Song 2017), with l1[n] += Σ|gx_n| and l2sq[n] += Σ gx_n²
+    (either may be None) (mia_jpeg_bwd_norms). x, g, gx: distinct fp32 (N,3,S,S); qtab as in
+    jpeg_roundtrip."""
+    N, S = _jpeg_args(x, qtab, (("g", g), ("gx", gx)))
+    _norm_outputs(N, l1, l2sq, nonfinite)
+    call("mia_jpeg_bwd_norms", ptr(x), ptr(g), ptr(gx), ptr(qtab), ptr(l1), ptr(l2sq), N, S,
+         ptr(nonfinite), stream())
+    return gx
+
+
 SI_MAX_SCALES = 8  # MIA_SI_MAX_SCALES
 
 

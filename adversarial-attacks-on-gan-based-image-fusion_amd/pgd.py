@@ -178,6 +178,7 @@ class AttackEngine:
         self.tap_numel = [64 * R * R, 64 * R * R, 128 * (R // 4) ** 2,
                           512 * ops.pool_out(R // 4, True) ** 2]
         self.rescales = 0  # loss-scale reductions of the last attack (overflow re-runs)
+        self.jp = None  # the JPEG stage of _step_gradient (set_jpeg): (qtab, grad), None = off
         self.set_loss_scale(loss_scale if loss_scale is not None
                             else DEFAULT_LOSS_SCALE[self.dtype])
 
@@ -309,6 +310,7 @@ class AttackEngine:
         A loss-scale overflow (fp16) lowers λ and re-runs the whole loop from the caller's
         patch, like PGD / Adam / C&W (the raw-gradient step would otherwise have written NaN /
         Inf into the patch)."""
+        self._no_jpeg("run_patch")
         patch0 = patch.clone()
 
         def once():
@@ -412,6 +414,7 @@ class AttackEngine:
         """``optimize_vgg`` literal mode (interpolation.py:743-843): Adam(lr) on the pixels,
         descending L, no ε-ball or clamp. The gradient carries the loss scale λ, so Adam's eps is
         scaled by λ too (m̂/(√v̂ + λ·eps) on λ·g ≡ m̂/(√v̂ + eps) on g)."""
+        self._no_jpeg("run_adam")
         return self._with_rescale(lambda: self._run_adam(x0, t, steps, lr, betas, eps), group)
 
     def _run_adam(self, x0, t, steps, lr, betas, eps):
@@ -434,6 +437,7 @@ class AttackEngine:
         best-L2 tracking with success = L_n(adv) < L_n(x0); early stop every steps//10 when the
         cost rises (one host sync there). See oracle.attack_ref.cw_attack. ``early_stop=False``
         runs every iteration (a fixed-work timing; not the reference's semantics)."""
+        self._no_jpeg("run_cw")
         return self._with_rescale(
             lambda: self._run_cw(x0, t, steps, c, lr, betas, eps, early_stop), group)
 
@@ -478,6 +482,7 @@ class AttackEngine:
 
     def run(self, x0, t, steps, eps, alpha, random_start=False, start_noise=None, group=None):
         """PGD-steps from x0 toward the objective; returns the adversarial images (new tensor)."""
+        self._no_jpeg("run")
         return self._with_rescale(
             lambda: self._run_pgd(x0, t, steps, eps, alpha, random_start, start_noise), group)
 
@@ -504,11 +509,23 @@ class AttackEngine:
         """The gradient a normalised step follows, with its per-image Σ|·| (l1) / Σ·² (l2sq, either
         may be None; device-resident): one chain of stages, each on or off.
 
+            once per step:     [x̃ = x + c·m → jp.x]  [J → jp.y]                 (with jp only)
             per scale copy i:  [x + c·m, S_i → si.x]  [D → di.x]  networks, assemble → g.full
                                [2^-i·g, /n on the last copy → g.si]
-            once per step:     [Dᵀ → g.di]  [taps ⊗ taps ⋆ → g.ti]
+            once per step:     [Dᵀ → g.di]  [J′(x̃)ᵀ → g.jp]  [taps ⊗ taps ⋆ → g.ti]
 
             g = W ⋆ Dᵀ (1/n)·Σ_i 2^-i·∇L(D S_i(x + c·m)),  S_i(t) = (t + 1)·2^-i − 1,  i = 0 … n − 1
+            g = W ⋆ J′(x̃)ᵀ Dᵀ (1/n)·Σ_i 2^-i·∇L(D S_i(J(x̃))),  x̃ = x + c·m            (with jp)
+
+        ``jp`` = self.jp = (qtab, grad), engine state set by set_jpeg() (None: off) rather than a
+        parameter, so every caller's signature stays what it was: the JPEG stage, closest to the
+        pixels because the saved file is what every later stage sees. qtab is the (2,64) fp32
+        device table (jpeg_quant_tables), grad 'cubic' or 'ste'. The look-ahead point x̃ is then
+        materialised first (ops.si_transform at s = 1; x itself without m), J runs once per step on
+        it (ops.jpeg_roundtrip) and the scale
+        copies read J(x̃) without a look-ahead; its adjoint runs once per step, after Dᵀ and before
+        the smoothing (ops.jpeg_bwd_norms, the surrogate of Shin & Song at x̃). 'ste' skips the
+        adjoint: J′ᵀ is taken as the identity (BPDA).
 
         ``m``: the Nesterov look-ahead (torchattacks NIFGSM), ``si_scales`` = n: the scale copies
         (SINIFGSM; ops.si_transform does both, and is skipped where it would be a bit copy: the
@@ -526,9 +543,16 @@ class AttackEngine:
         n = int(si_scales)
         if not 1 <= n <= SI_MAX_SCALES:
             raise ValueError(f"si_scales must be an integer in 1 … {SI_MAX_SCALES}")
+        xt, jp = None, self.jp
+        if jp is not None:
+            qtab, jp_grad = jp
+            xt = x if m is None else ops.si_transform(x, m, ws.get("jp.x", x.shape, f32), c, 1.0)
+            x, m = ops.jpeg_roundtrip(xt, ws.get("jp.y", x.shape, f32), qtab), None
+            if jp_grad == "ste":
+                xt = None
         accumulate = m is not None or si_scales != 1
-        last_stage = ("ti" if taps is not None else "di" if di is not None
-                      else "si" if accumulate else "full")
+        last_stage = ("ti" if taps is not None else "jp" if xt is not None
+                      else "di" if di is not None else "si" if accumulate else "full")
 
         def sums(stage, last_copy=True):
             return (l1, l2sq) if stage == last_stage and last_copy else (None, None)
@@ -556,6 +580,9 @@ class AttackEngine:
         if di is not None:
             out = ops.di_resize_pad_bwd_norms(out, ws.get("g.di", x.shape, f32), *sums("di"), *di,
                                               nonfinite=flag)
+        if xt is not None:
+            out = ops.jpeg_bwd_norms(xt, out, ws.get("g.jp", x.shape, f32), qtab, *sums("jp"),
+                                     nonfinite=flag)
         if taps is not None:
             out = ops.ti_smooth_norms(out, taps, ws.get("g.ti", x.shape, f32), *sums("ti"),
                                       nonfinite=flag)
@@ -568,13 +595,39 @@ class AttackEngine:
             raise ValueError("ti_taps must hold an odd number of values, 1 … 63")
         return t.to(torch.float32).to(self.G.device).contiguous()
 
+    def _no_jpeg(self, what):
+        """The runners that take no gradient through _step_gradient's chain, or that attack()
+        rejects together with jpeg_quality, refuse to start while the JPEG stage is on: it would
+        be ignored or enter a composition that nothing tests."""
+        if self.jp is not None:
+            raise ValueError(f"{what} does not combine with the JPEG stage: call set_jpeg(None) "
+                             "first (run_mi, run_pi and run_l2 are the runs that take it)")
+
+    def set_jpeg(self, jpeg_quality, jpeg_grad="cubic"):
+        """Turn the JPEG stage of _step_gradient on (``jpeg_quality`` an integer in 1 … 100,
+        ``jpeg_grad`` 'cubic' or 'ste') or off (None): self.jp = (the quantiser steps of
+        jpeg_quant_tables as (2,64) fp32 on the engine's device, the gradient mode), or None. It
+        is engine state, like the loss scale: step_l2 / step_mi / step_pi and the run_* wrappers
+        keep their signatures and every gradient they take goes through the stage until it is
+        turned off — step_l2 / step_mi / step_pi, run_l2 / run_mi / run_pi and whatever else
+        calls _step_gradient. The other runners (run, run_adam, run_cw, run_spsa, run_universal,
+        run_apgd, run_sign_hunter, run_patch) raise while it is on (_no_jpeg), as attack()
+        rejects those combinations by name. Returns self.jp."""
+        self.jp = None
+        if jpeg_quality is not None:
+            if self.size % 8:
+                raise ValueError("jpeg_quality needs an image size that is a multiple of 8")
+            qtab = jpeg_quant_tables(jpeg_quality).to(torch.float32).to(self.G.device)
+            self.jp = (qtab.contiguous(), _check_jpeg_grad(jpeg_grad))
+        return self.jp
+
     def step_l2(self, x, a, e, ti_taps=None, di=None, si_scales=1):
         """One L2-ball PGD step on x in place (after prepare()); a, e in [-1,1] units.
         ``ti_taps`` (fp32 device taps, ti_device_taps): the step follows the smoothed gradient.
         ``di`` (a make_di_schedule row (rnd, top, left, apply) of host integers): with apply = 1
         the gradient is Dᵀ ∇L(D x); apply = 0 or None is the plain step.
         ``si_scales`` > 1: the gradient is the mean over that many scale copies; 1 is the step
-        without them (_step_gradient for all three)."""
+        without them (_step_gradient for all three; after set_jpeg() the JPEG stage too)."""
         # sums: Σg², Σ(adv − x0)² per image
         sums = ops.zero_(self.ws.get("norm.sums", (2, x.shape[0]), torch.float32))
         g = self._step_gradient(x, si_scales=si_scales, di=_di_row(di), taps=ti_taps,
@@ -594,7 +647,8 @@ class AttackEngine:
         own buffers are overwritten by the next pass; ops.vt_combine_norms then forms gt (vt.gt)
         and the new v together. On the last step (``vt.last``) the neighbours are skipped: v is
         never read again. The TI smoothing, if ``taps``, acts on gt; l1 receives Σ|·| of what
-        the update kernel reads, which is returned."""
+        the update kernel reads, which is returned. After set_jpeg() G includes the JPEG stage,
+        J and its adjoint at x_nes and at every neighbour (it is part of _step_gradient)."""
         ws, f32 = self.ws, torch.float32
         g = ws.get("vt.g", x.shape, f32)
         g.copy_(self._step_gradient(x, m, c, si_scales, di))
@@ -629,7 +683,8 @@ class AttackEngine:
         SINIFGSM; _step_gradient for all four). ``vt`` (a VtStep: samples, r, seed, image0, step,
         last): the variance-tuned step (torchattacks VMIFGSM, _vt_grad_norms) on the variance
         buffer ws "vt.v", with the neighbour noise of step index ``vt.step``; None is the step
-        without it. The update rule is the same in every case."""
+        without it. After set_jpeg(quality, grad) it is the JPEG-robust step, on the gradient of
+        the objective at J(x) (_step_gradient). The update rule is the same in every case."""
         g, l1 = self._mi_gradient(x, m, momentum, a, ti_taps, di, nesterov, si_scales, vt)
         ops.mi_update(x, self.x0, g, l1, m, _f32(momentum), _f32(a), _f32(e),
                       nonfinite=self.nonfinite)
@@ -678,7 +733,9 @@ class AttackEngine:
         Dₖᵀ ∇L(Dₖ x) (smoothed after the adjoint when ti_taps is given). The schedule is host
         data fixed before the loop, so an fp16 loss-scale re-run replays the same draws.
         ``si_scales`` (1 … SI_MAX_SCALES): every step follows the mean gradient over that many
-        scale copies (_step_gradient; one Dₖ serves all copies of step k)."""
+        scale copies (_step_gradient; one Dₖ serves all copies of step k).
+        After set_jpeg(quality, grad) every step follows the gradient of the objective at J(x),
+        the JPEG round trip of the iterate."""
         taps = None if ti_taps is None else self.ti_device_taps(ti_taps)
         rows = _di_rows(di, steps, self.size)
         n_si = _check_si_scales(si_scales)
@@ -718,7 +775,13 @@ class AttackEngine:
         gradient before the smoothing (_vt_grad_norms). u_{k,i} is counter-based noise, a pure
         function of (vt_seed, vt_first_image + n, k, i, element): a loss-scale re-run starts from
         v = 0 and replays the same noise, and an image's result does not depend on the batch. The
-        last step draws no neighbours."""
+        last step draws no neighbours.
+        After set_jpeg(quality, grad): the JPEG-robust attack — every gradient above is that of the
+        objective at J(·), the round trip through a baseline 4:4:4 JPEG of that quality
+        (ops.jpeg_roundtrip, once per gradient, at the look-ahead point), pulled back through J by
+        ``grad``: 'cubic', the adjoint of Shin & Song's surrogate (ops.jpeg_bwd_norms, after Dₖᵀ
+        and before the smoothing), or 'ste', the identity. The iterate itself stays
+        uncompressed."""
         return self._with_rescale(self._mi_runner(
             x0, t, steps, eps, alpha, momentum, random_start, start_noise, ti_taps, di, nesterov,
             si_scales, vt_samples, vt_beta, vt_seed, vt_first_image), group)
@@ -753,8 +816,8 @@ class AttackEngine:
             A ← A' + p;  x ← clamp(x0 + clamp(x + ab·s + p − x0, −e, e), −1, 1)
         (one fused HIP kernel, ops.pi_update; S is a chain of fp32 additions in a fixed order, zero
         padded, see include/miattack.h). g is run_mi's gradient with every option of it:
-        ``ti_taps``, ``di``, ``si_scales``, ``vt_*`` and ``nesterov``, whose look-ahead is
-        x + μ·ab·m. m and A ping-pong between two workspace buffers each (mi.m / mi.m1, pi.a0 /
+        ``ti_taps``, ``di``, ``si_scales``, ``vt_*``, set_jpeg() and ``nesterov``, whose look-ahead
+        is x + μ·ab·m. m and A ping-pong between two workspace buffers each (mi.m / mi.m1, pi.a0 /
         pi.a1), swapped every step. A random start and an fp16 loss-scale re-run begin from
         A = 0. There is no host read-back in the loop. γ = 0 gives run_mi with a = ab; β = 1 with
         steps·alpha ≤ eps gives run_mi, both bit for bit."""
@@ -852,6 +915,7 @@ class AttackEngine:
         result depends on neither the batch nor the world size. An estimate that is entirely
         zero under 'linf' (every pair with f⁺ = f⁻) is reported like an overflow (0/0), as an
         all-zero gradient is by run_mi."""
+        self._no_jpeg("run_spsa")
         if norm not in ("linf", "l2"):
             raise ValueError("SPSA is implemented for norm='linf' and 'l2' only")
         q = _check_spsa_samples(spsa_samples)
@@ -931,6 +995,7 @@ class AttackEngine:
         per step, the one attack with a collective in its data path). Returns the batch
         clamp(x0 + δ) (new tensor); δ is kept in self.uap_delta (a clone, on the device). An fp16
         loss-scale re-run restarts from δ₀."""
+        self._no_jpeg("run_universal")
         return self._with_rescale(
             lambda: self._run_universal(x0, t, steps, eps, alpha, random_start, start_noise,
                                         group), group)
@@ -1020,6 +1085,7 @@ class AttackEngine:
         One deviation from torchattacks: at the first checkpoint its check_oscillation compares
         step 0 with loss_steps[-1], a zero row reached by negative indexing; here step 0 is
         compared with the objective at the starting point, the paper's condition."""
+        self._no_jpeg("run_apgd")
         return self._with_rescale(
             lambda: self._run_apgd(x0, t, steps, eps, random_start, start_noise), group)
 
@@ -1115,6 +1181,7 @@ class AttackEngine:
         buffers ``sh.*``): no per-query host synchronisation. The schedule depends on the image
         size alone, so reruns are bit-identical and an image's result depends on neither the
         batch nor the world size."""
+        self._no_jpeg("run_sign_hunter")
         steps = int(steps)
         self.sh_queries = steps + 1 if steps > 0 else 0
         return self._with_rescale(lambda: self._run_sign_hunter(x0, t, steps, eps), group)
@@ -1352,6 +1419,67 @@ def _check_spsa_first_image(spsa_first_image, n):
     return int(spsa_first_image)
 
 
+# ITU T.81 Annex K, tables K.1 (luminance) and K.2 (chrominance), natural (row-major) order
+JPEG_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55,
+             14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+             18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+               24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+JPEG_GRADS = ("cubic", "ste")
+
+
+def _check_jpeg_quality(quality):
+    """attack()'s ``jpeg_quality`` / jpeg_compress's ``quality``: an integer in 1 … 100."""
+    if (isinstance(quality, (bool, np.bool_)) or not isinstance(quality, (int, np.integer))
+            or not 1 <= quality <= 100):
+        raise ValueError("jpeg_quality must be None or an integer in 1 … 100")
+    return int(quality)
+
+
+def _check_jpeg_grad(jpeg_grad):
+    """attack()'s ``jpeg_grad``: 'cubic' (the surrogate's adjoint) or 'ste' (the identity)."""
+    if jpeg_grad not in JPEG_GRADS:
+        raise ValueError(f"jpeg_grad must be one of {JPEG_GRADS}")
+    return jpeg_grad
+
+
+def jpeg_quant_tables(quality):
+    """The quantiser steps a baseline JPEG of ``quality`` (an integer in 1 … 100) is written with:
+    an int64 (2,64) host tensor, luminance then chrominance, natural order — the Annex K tables T
+    under the IJG scaling s = 5000 // q if q < 50 else 200 − 2·q,
+    Q = clamp((T·s + 50) // 100, 1, 255) (what libjpeg / Pillow write at that quality)."""
+    q = _check_jpeg_quality(quality)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    t = torch.tensor([JPEG_LUMA, JPEG_CHROMA], dtype=torch.int64)
+    return torch.clamp((t * s + 50) // 100, 1, 255)
+
+
+def jpeg_dct_matrix():
+    """The orthonormal 8 × 8 DCT-II matrix of the JPEG kernels, fp32 (8,8):
+    D[u][i] = c(u)/2·cos((2i+1)·u·π/16), c(0) = 1/√2, evaluated in fp64 and rounded once."""
+    u = torch.arange(8, dtype=torch.float64).reshape(8, 1)
+    i = torch.arange(8, dtype=torch.float64).reshape(1, 8)
+    d = 0.5 * torch.cos((2 * i + 1) * u * (np.pi / 16))
+    d[0] = 0.5 / np.sqrt(2.0)
+    return d.to(torch.float32)
+
+
+def jpeg_compress(imgs, quality):
+    """J(imgs): what saving the images as baseline 4:4:4 JPEGs of ``quality`` and loading them
+    again does to them, on the HIP kernel the attack itself uses (ops.jpeg_roundtrip). imgs:
+    (N,3,S,S) floating point in [-1,1] ON THE GPU, S a multiple of 8, not modified. Returns fp32
+    images on the same device."""
+    if not torch.is_tensor(imgs) or imgs.dim() != 4 or imgs.shape[1] != 3 \
+            or not imgs.is_floating_point():
+        raise ValueError("imgs must be an (N,3,S,S) floating point tensor")
+    if not imgs.is_cuda:
+        raise ValueError("jpeg_compress runs on the GPU only: pass device tensors")
+    qtab = jpeg_quant_tables(quality).to(imgs.device, torch.float32)
+    x = imgs.detach().to(torch.float32).contiguous()
+    return ops.jpeg_roundtrip(x, torch.empty_like(x), qtab)
+
+
 def ti_gaussian_taps(kernlen=15, nsig=3.0):
     """The 1-D taps of torchattacks TIFGSM's Gaussian kernel, fp64: k/Σk with k = exp(−x²/2) on
     linspace(−nsig, nsig, kernlen). torchattacks' gkern (scipy.stats.norm.pdf, whose 1/√(2π)
@@ -1494,7 +1622,9 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
            seed=0, start_noise=None, norm="linf", momentum=None, loss="gan_vgg", loss_scale=None,
            lr=0.01, cw_c=1e-4, return_info=False, group=None, ti_kernel=None, ti_nsig=3.0,
            di_prob=None, di_resize_rate=0.9, di_schedule=None, nesterov=False, si_scales=None,
-           pi_amplification=None, pi_kernel=3, pi_project=1.0, vt_samples=None, vt_beta=1.5, vt_first_image=0, sign_hunter=False, universal=False,
+           pi_amplification=None, pi_kernel=3, pi_project=1.0, jpeg_quality=None,
+           jpeg_grad="cubic", vt_samples=None, vt_beta=1.5, vt_first_image=0, sign_hunter=False,
+           universal=False,
            spsa_samples=None, spsa_delta=0.01, spsa_first_image=0, apgd=False):
     """Craft adversarial images against the GAN fusion pipeline.
 
@@ -1725,9 +1855,31 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             vt_samples or pi_amplification. With return_info, info["apgd"] holds ``loss`` and ``step_size``
             (steps + 1, N: the start, then after every step), ``best_step`` (0 = the start,
             i + 1 = step i) and ``halvings`` per image, as host tensors.
+    jpeg_quality  None (default): the attack assumes the pipeline reads the fp32 tensor it returns.
+            An integer q in 1 … 100, with norm='linf' or 'l2': the JPEG-robust attack, for an
+            adversarial image that is saved as a .jpg before the pipeline reads it (as the
+            reference saves its inputs, interpolation.py:323-325). Every step follows the gradient
+            of the objective at J(x), the round trip of the iterate through a baseline 4:4:4 JPEG
+            of quality q (8-bit pixels, JFIF YCbCr, 8 × 8 DCT, the IJG-scaled Annex K tables
+            ``jpeg_quant_tables(q)``; fused HIP kernels, the arithmetic in include/miattack.h).
+            The stage sits closest to the pixels; with x̃ = x + μ·a·m under nesterov, else x:
+                      g = W ⋆ J′(x̃)ᵀ Dᵀ (1/n)·Σ_i 2^-i·∇L(D S_i(J(x̃)))
+            J runs once per gradient, its adjoint once, after Dᵀ and before the smoothing W; the
+            targets stay those of x0 and t. norm='linf' takes the MIFGSM rule (momentum=None
+            means μ = 0, as with ti_kernel / di_prob), 'l2' the PGDL2 rule. It composes with
+            momentum, nesterov, ti_kernel, di_prob / di_schedule, si_scales, vt_samples,
+            pi_amplification and random_start, and not with apgd, universal, sign_hunter,
+            spsa_samples or norm 'adam' / 'l2_cw'. The image returned is the UNCOMPRESSED iterate,
+            which the caller then saves; ``jpeg_compress(adv, q)`` is what the pipeline will see.
+            4:2:0 chroma subsampling and sizes that are no multiple of 8 are not implemented.
+    jpeg_grad  how the gradient passes the coefficient rounding of J (needs jpeg_quality):
+            'cubic' (default) — the adjoint of the surrogate round(v) + (v − round(v))³ of Shin &
+            Song (2017), derivative 3·(v − round(v))², one fused HIP kernel that recomputes the
+            coefficients from x̃; 'ste' — straight through, J′ᵀ taken as the identity (BPDA).
     group   process group of a data-parallel job (``dist.attack_distributed``): the fp16
             loss-scale re-run decision is all-reduced over it so every shard runs at one λ.
-    Returns the adversarial images on the input's device (fp32), and a dict if return_info.
+    Returns the adversarial images on the input's device (fp32), and a dict if return_info
+    (with jpeg_quality it holds ``loss_jpeg``, the per-image objective at J(adv), next to ``loss``).
     """
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}")
@@ -1744,6 +1896,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
             ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
             ("pi_amplification", pi_amplification is not None),
+            ("jpeg_quality", jpeg_quality is not None),
             ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd)),
             ("universal", not isinstance(universal, (bool, np.bool_)) or bool(universal)),
             ("random_start", bool(random_start))) if on]
@@ -1765,6 +1918,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
             ("vt_samples", vt_samples is not None), ("spsa_samples", spsa_samples is not None),
             ("pi_amplification", pi_amplification is not None),
+            ("jpeg_quality", jpeg_quality is not None),
             ("apgd", not isinstance(apgd, (bool, np.bool_)) or bool(apgd)),
             ("sign_hunter", sign_hunter)) if on]
         if mixed:
@@ -1784,7 +1938,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("di_schedule", di_schedule is not None), ("si_scales", si_scales is not None),
             ("vt_samples", vt_samples is not None),
             ("pi_amplification", pi_amplification is not None),
-            ("sign_hunter", sign_hunter)) if on]
+            ("jpeg_quality", jpeg_quality is not None), ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"apgd (Auto-PGD) does not combine with {', '.join(mixed)}: it has "
                              "its own momentum and step-size rule")
@@ -1830,6 +1984,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
             ("di_prob", di_prob is not None), ("di_schedule", di_schedule is not None),
             ("si_scales", si_scales is not None), ("vt_samples", vt_samples is not None),
             ("pi_amplification", pi_amplification is not None),
+            ("jpeg_quality", jpeg_quality is not None),
             ("apgd", apgd), ("sign_hunter", sign_hunter)) if on]
         if mixed:
             raise ValueError(f"spsa_samples (SPSA) does not combine with {', '.join(mixed)}: "
@@ -1846,9 +2001,21 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
         _check_pi_amplification(pi_amplification)
         if norm != "linf":
             raise ValueError("pi_amplification (PI-FGSM) is implemented for norm='linf' only")
+    jpeg_grad = _check_jpeg_grad(jpeg_grad)
+    if jpeg_quality is None:
+        if jpeg_grad != "cubic":
+            raise ValueError("jpeg_grad needs jpeg_quality (the JPEG stage is off without it)")
+    else:
+        jpeg_quality = _check_jpeg_quality(jpeg_quality)
+        if norm not in ("linf", "l2"):
+            raise ValueError("jpeg_quality (the JPEG-robust attack) is implemented for "
+                             "norm='linf' and 'l2' only")
     if loss != "gan_vgg":
         raise ValueError("only loss='gan_vgg' (the optimize_vgg objective) is implemented")
     size = net.decoder.size
+    if jpeg_quality is not None and size % 8:
+        raise ValueError("jpeg_quality needs an image size that is a multiple of 8 (JPEG's edge "
+                         "replication is not implemented)")
     _check_images(imgs, size, "imgs")
     vt_first_image = _check_vt_first_image(vt_first_image, imgs.shape[0])
     spsa_first_image = _check_spsa_first_image(spsa_first_image, imgs.shape[0])
@@ -1902,6 +2069,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
     x0 = imgs.detach().to(dev, torch.float32).contiguous()
     t = target.detach().to(dev, torch.float32).contiguous()
     eng = AttackEngine(net.encoder.impl, net.decoder.impl, vgg.impl, loss_scale=loss_scale)
+    eng.set_jpeg(jpeg_quality, jpeg_grad)  # the stage of every gradient the run_* below take
     noise = None
     if random_start:
         noise_shape = (1,) + tuple(x0.shape[1:]) if universal else tuple(x0.shape)
@@ -1931,7 +2099,7 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                          vt_seed=(int(seed) + VT_SEED_OFFSET) % (1 << 64),
                          vt_first_image=vt_first_image)
     elif norm == "linf" and (momentum is not None or ti_taps is not None or di is not None
-                             or n_si > 1 or n_vt is not None):
+                             or n_si > 1 or n_vt is not None or jpeg_quality is not None):
         adv = eng.run_mi(x0, t, int(steps), float(eps), float(alpha),
                          float(momentum) if momentum is not None else 0.0, random_start, noise,
                          group=group, ti_taps=ti_taps, di=di, nesterov=nesterov, si_scales=n_si,
@@ -1963,7 +2131,11 @@ def attack(net, imgs, eps, steps, *, target=None, vgg=None, alpha=0.01, random_s
                     pi_kernel=pi_kernel if pi_amplification is not None else None,
                     pi_project=pi_project if pi_amplification is not None else None,
                     queries=(2 * n_spsa * int(steps) if n_spsa is not None
-                             else eng.sh_queries if sign_hunter else 0))
+                             else eng.sh_queries if sign_hunter else 0),
+                    jpeg_quality=jpeg_quality,
+                    jpeg_grad=jpeg_grad if jpeg_quality is not None else None,
+                    loss_jpeg=(eng.loss(jpeg_compress(adv.to(dev), jpeg_quality))
+                               if jpeg_quality is not None else None))
         if sign_hunter:
             info["sign_hunter"] = eng.sign_hunter_info()
         if universal:
@@ -1982,7 +2154,7 @@ def fgsm(net, imgs, eps, **kw):
     black-box form, the sign of the SPSA estimate; ``universal=True`` is the one-step universal
     perturbation, δ = e·sign of the summed normalised gradients). ``apgd=True`` is rejected: one step
     of Auto-PGD (step size 2·e, the better of the start and the step returned) is not FGSM.
-    ``sign_hunter=True`` is rejected too: SignHunter follows no gradient.
+    ``sign_hunter=True`` is rejected too: SignHunter follows no gradient. So is ``jpeg_quality``.
     ``pi_amplification=β`` is forwarded, the one-step patch-wise attack: every pixel moves by
     β·ε·s, s the sign of its gradient, its overflow (β − 1)·ε·s (β > 1) votes in its neighbours'
     windows, and a pixel receives p = ±pi_project·β·ε by the sign of the votes it gets before the
@@ -1996,6 +2168,9 @@ def fgsm(net, imgs, eps, **kw):
     if kw.get("apgd"):
         raise ValueError("fgsm() takes no apgd: one step of Auto-PGD is not FGSM; call "
                          "attack(..., steps=1, apgd=True) for that")
+    if kw.get("jpeg_quality") is not None:
+        raise ValueError("fgsm() takes no jpeg_quality: the JPEG-robust attack is iterative; call "
+                         "attack(..., steps=1, jpeg_quality=q) for one step of it")
     kw.pop("alpha", None)
     kw.pop("random_start", None)
     return attack(net, imgs, eps, 1, alpha=eps, random_start=False, **kw)

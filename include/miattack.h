@@ -480,6 +480,47 @@ int mia_di_resize_pad(const float* x, float* y, int N, int C, int S, int rnd, in
  * bit for bit. nonfinite (NULL or int[N]) is set for an image with a non-finite element of gx. */
 int mia_di_resize_pad_bwd_norms(const float* g, float* gx, float* l1, float* l2sq, int N, int C,
                                 int S, int rnd, int top, int left, int* nonfinite, void* stream);
+/* The JPEG round trip y = J(x): what saving an image as a baseline 4:4:4 JPEG and loading it again
+ * does to it (entropy coding is lossless and left out). x, y: fp32 (N,3,S,S) in [-1,1], distinct
+ * buffers; qtab: 2 × 64 fp32 quantiser steps in device memory, luminance then chrominance, natural
+ * (row-major) order, distinct from x and y. S a multiple of 8, ≥ 8; 3·S² < 2^31; N in 1 … 65535
+ * (anything else: MIA_EINVAL before any launch). Per pixel and 8 × 8 block, every operation one
+ * fp32 rounding, no contraction, in this order:
+ *   1. p = floor(clamp((x + 1)·127.5 + 0.5, 0, 255))                  (torchvision save_image)
+ *   2. Y  = 0.299·R + 0.587·G + 0.114·B − 128;  Cb = −0.168736·R − 0.331264·G + 0.5·B;
+ *      Cr = 0.5·R − 0.418688·G − 0.081312·B     (coefficients rounded to fp32, products added
+ *      left to right; the ±128 of Cb and Cr cancels against step 5 and is left out)
+ *   3. F = D·B·Dᵀ, D[u][i] = c(u)/2·cos((2i+1)uπ/16), c(0) = 1/√2, evaluated in fp64 and rounded
+ *      once to fp32: rows first, then columns, each output d[0]·v[0], then + d[k]·v[k], k = 1 … 7
+ *   4. v = F / Q (IEEE division);  r = rint(v) (half to even);  F' = r·Q
+ *   5. o = Dᵀ·F'·D, columns first, then rows, the same summation order;  Y + 128;
+ *      R = Y + 1.402·Cr;  G = (Y − 0.344136·Cb) − 0.714136·Cr;  B = Y + 1.772·Cb;
+ *      p' = clamp(rint(·), 0, 255);  y = p'/127.5 − 1
+ * so the result equals the torch fp32 CPU ops bit for bit. One block owns a 64 × 32 tile of all
+ * three planes of one image: an image's result depends on its own planes only, and reruns are
+ * bit-identical. 16-byte aligned x / y move 16-byte vectors, anything else scalars (the same
+ * bits). 4:2:0 subsampling and sizes that are no multiple of 8 are not implemented. */
+int mia_jpeg_roundtrip(const float* x, float* y, const float* qtab, int N, int S, void* stream);
+/* The adjoint at x of the round trip's differentiable surrogate (Shin & Song 2017: round(v)
+ * replaced by round(v) + (v − round(v))³ in step 4, derivative w = 3·(v − rint(v))², continuous
+ * across ties; the 8-bit roundings and clamps of steps 1 and 5 pass the gradient through, the
+ * 127.5 factors and Q cancel), with the per-image norms of the result, in one pass:
+ *   gx = Aᵀ·IDCT(w ⊙ DCT(Mᵀ·g)),  l1[n] += Σ|gx_n|,  l2sq[n] += Σ gx_n²   (fp32 [N], either may be
+ *   NULL; ordered reductions as in mia_grad_assemble_norms: one partial per 64 × 32 tile, a
+ *   geometry that depends on S only; gx² enters through an fma).
+ * A is the RGB → YCbCr matrix of step 2, M the YCbCr → RGB matrix of step 5, DCT / IDCT the passes
+ * of steps 3 and 5 (D is orthonormal, so IDCTᵀ = DCT). In order, one fp32 rounding each:
+ *   h_Y = (g_R + g_G) + g_B;  h_Cb = −0.344136·g_G + 1.772·g_B;  h_Cr = 1.402·g_R − 0.714136·g_G
+ *   H = DCT(h);  v of steps 1 – 4 at x;  d = v − rint(v);  w = 3·(d·d);  T = w·H;  u = IDCT(T)
+ *   gx_R = (0.299·u_Y − 0.168736·u_Cb) + 0.5·u_Cr;  gx_G = (0.587·u_Y − 0.331264·u_Cb) − 0.418688·u_Cr
+ *   gx_B = (0.114·u_Y + 0.5·u_Cb) − 0.081312·u_Cr
+ * The launch recomputes v from x: nothing is stored between the forward and the adjoint. x, g,
+ * gx: fp32 (N,3,S,S), distinct buffers; qtab, S, N as above (anything else: MIA_EINVAL before any
+ * launch). nonfinite (NULL or int[N]) is set for an image with a non-finite element of gx. Reruns
+ * are bit-identical, an image's gx and sums do not depend on the other images, and the vector and
+ * scalar forms give the same bits, sums included. */
+int mia_jpeg_bwd_norms(const float* x, const float* g, float* gx, const float* qtab, float* l1,
+                       float* l2sq, int N, int S, int* nonfinite, void* stream);
 /* Scale-invariant and Nesterov attacks (torchattacks SINIFGSM / NIFGSM), images in [-1,1].
  * The input of scale copy i at the look-ahead point, per element:
  *   t = m ? x + c·m : x   (c = μ·a; the product rounded, then the sum)

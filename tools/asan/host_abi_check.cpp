@@ -223,6 +223,48 @@ int main() {
                                            nullptr, nullptr), "di bwd N");
   expect_error(mia_di_resize_pad_bwd_norms(di_a, di_b, dummy, dummy, 2, 3, 46341, 3, 0, 1,
                                            nullptr, nullptr), "di bwd S*S >= 2^31");
+  // JPEG round trip and its adjoint: null / aliased / overlapping buffers, sizes that are no
+  // multiple of 8 or overflow (1 image of 3 × 8 × 8 = 192 floats per buffer, a table of 128)
+  static float jp_buf[4 * 192 + 128];
+  float* jp_x = jp_buf;
+  float* jp_y = jp_buf + 192;
+  float* jp_g = jp_buf + 384;
+  float* jp_q = jp_buf + 768;
+  expect_error(mia_jpeg_roundtrip(nullptr, jp_y, jp_q, 1, 8, nullptr), "jpeg null x");
+  expect_error(mia_jpeg_roundtrip(jp_x, nullptr, jp_q, 1, 8, nullptr), "jpeg null y");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, nullptr, 1, 8, nullptr), "jpeg null qtab");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_x, jp_q, 1, 8, nullptr), "jpeg in place");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_x + 191, jp_q, 1, 8, nullptr), "jpeg overlap");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_q - 191, jp_q, 1, 8, nullptr), "jpeg y over qtab");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_x + 64, 1, 8, nullptr), "jpeg qtab inside x");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1, 12, nullptr), "jpeg S = 12");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1, 4, nullptr), "jpeg S < 8");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1, 0, nullptr), "jpeg S 0");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1, -8, nullptr), "jpeg S < 0");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1, 26760, nullptr), "jpeg 3*S*S >= 2^31");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1, 1 << 30, nullptr), "jpeg S*S overflows");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 0, 8, nullptr), "jpeg N 0");
+  expect_error(mia_jpeg_roundtrip(jp_x, jp_y, jp_q, 1 << 16, 8, nullptr), "jpeg N");
+  expect_error(mia_jpeg_bwd_norms(nullptr, jp_g, jp_y, jp_q, dummy, dummy, 1, 8, nullptr, nullptr),
+               "jpeg bwd null x");
+  expect_error(mia_jpeg_bwd_norms(jp_x, nullptr, jp_y, jp_q, dummy, dummy, 1, 8, nullptr, nullptr),
+               "jpeg bwd null g");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, nullptr, jp_q, nullptr, nullptr, 1, 8, nullptr,
+                                  nullptr), "jpeg bwd null gx");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, jp_y, nullptr, dummy, dummy, 1, 8, nullptr, nullptr),
+               "jpeg bwd null qtab");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, jp_g, jp_q, dummy, dummy, 1, 8, nullptr, nullptr),
+               "jpeg bwd in place");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_x, jp_y, jp_q, dummy, dummy, 1, 8, nullptr, nullptr),
+               "jpeg bwd g is x");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, jp_x + 100, jp_q, dummy, dummy, 1, 8, nullptr,
+                                  nullptr), "jpeg bwd gx over x");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, jp_y, jp_q, dummy, dummy, 1, 12, nullptr, nullptr),
+               "jpeg bwd S = 12");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, jp_y, jp_q, dummy, dummy, 1, 26760, nullptr, nullptr),
+               "jpeg bwd 3*S*S >= 2^31");
+  expect_error(mia_jpeg_bwd_norms(jp_x, jp_g, jp_y, jp_q, dummy, dummy, 70000, 8, nullptr, nullptr),
+               "jpeg bwd N");
   // scale copies / look-ahead: null / aliased / overlapping buffers, scales that are no 2^-i,
   // sizes (2 images of 48 floats per buffer: di_a and di_b are disjoint)
   expect_error(mia_si_transform(nullptr, nullptr, di_b, 2, 48, 0.f, 0.5f, nullptr), "si null x");
